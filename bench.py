@@ -7,6 +7,12 @@ CE -> backward -> gradient all-reduce -> ACM momentum SGD), fp32, on synthetic
 
 A "step" = one full training iteration of every rank on its own 2 images.  Inputs are
 resident in HBM before the timed region.  One JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line (plus the outputs of
+the last timed step with --dump-outputs).  Everything else it can measure or check - the
+deferred-update route, the N-rank projections, the conv body and RoIPool alone, the other
+arithmetic plans and the in-run parity check, configs[3] / configs[4], the CPU baseline, and
+at N > 1 the bare exchange and the route A/B - runs only with --full.
 """
 import argparse
 import json
@@ -128,6 +134,14 @@ def parse():
     ap.add_argument('--infer-rois', type=int, default=4000)
     ap.add_argument('--infer-height', type=int, default=375)
     ap.add_argument('--infer-width', type=int, default=500)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every other measurement and check (the '
+                         'deferred route, projections, conv / RoIPool alone, the other plans and '
+                         'the parity check, configs[3] / configs[4], the CPU baseline; N > 1: the '
+                         'bare exchange and the route A/B); the --no-* options still drop parts')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned as '
+                         'DIR/<name>.npy (float32; the parameters as a fixed seeded sample)')
     return ap.parse_args()
 
 
@@ -137,10 +151,42 @@ def infer_main(args):
     import torch
     torch.cuda.set_device(0)
     emit(infer_measure(args, torch.device('cuda', 0), max(args.steps // 4, 4),
-                       max(args.warmup // 4, 2)))
+                       max(args.warmup // 4, 2), dump=args.dump_outputs))
 
 
-def infer_measure(args, dev, steps, warmup):
+DUMP_LIMIT_BYTES = 64 << 20
+PARAM_SAMPLE = 1 << 20        # parameters in the dumped sample (the arena holds 239 M)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 (float64 stays float64)."""
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        sys.exit('bench.py: %d bytes of outputs exceed the %d-byte dump limit' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+def train_outputs(eng, out):
+    """What the timed training step hands back: train_step's dict (per-image losses, class
+    probabilities, gate weights, fc8 logits and their gradient) and the parameters the step left,
+    as a sample at fixed seeded positions of the flat arena."""
+    import numpy as np
+    import torch
+    arrays = {k: v.detach().cpu().numpy() for k, v in out.items() if torch.is_tensor(v)}
+    p = eng.state_tensors()['params']
+    idx = np.unique(np.random.default_rng(0).integers(0, p.numel(), PARAM_SAMPLE))
+    arrays['params_sample'] = p[torch.from_numpy(idx).to(p.device)].cpu().numpy()
+    return arrays
+
+
+def infer_measure(args, dev, steps, warmup, dump=''):
     """configs[4]: `steps` synthetic images through the yaml's 10-pass TTA end to end, the fc6
     forward launches of every pass timed with HIP events (engine.timing_events)."""
     import numpy as np
@@ -167,6 +213,8 @@ def infer_measure(args, dev, steps, warmup):
            for e in entries]
     assert test_wsl.device_post_supported(ex, ims[0])
 
+    last = []
+
     def run(k):
         n = 0
         for i in range(k):
@@ -174,6 +222,7 @@ def infer_measure(args, dev, steps, warmup):
             cls_boxes = test_wsl.im_detect_all(ex, ims[i % len(ims)], e['boxes'], e['obn_scores'])
             n += sum(len(b) for b in cls_boxes[1:])
         torch.cuda.synchronize()
+        last[:] = [cls_boxes] if k else []
         return n
     run(warmup)
     ev = []
@@ -185,6 +234,12 @@ def infer_measure(args, dev, steps, warmup):
     dt = time.perf_counter() - t0
     if eng is not None:
         eng.timing_events = None
+    if dump:
+        # the last image's detections: one row per box, (class, x1, y1, x2, y2, score)
+        rows = [np.concatenate([np.full((len(b), 1), j, np.float32), np.asarray(b, np.float32)], 1)
+                for j, b in enumerate(last[0]) if j > 0 and len(b)]
+        dets = np.concatenate(rows, 0) if rows else np.zeros((0, 6), np.float32)
+        dump_outputs(dump, {'detections': dets})
     fc6_ms = sum(a.elapsed_time(b) for a, b in ev) / steps if ev else None
     passes = test_wsl.tta_passes()
     # algorithmic work per image (conv 463.7 GFLOP at 600x1000, scaled by the
@@ -1034,6 +1089,8 @@ def n_rank_prologue(job, pg, rank, world, args, hb):
         print('bench.py: ranks differ AFTER the parameter broadcast: %s' % ','.join(bad),
               file=sys.stderr, flush=True)
         sys.exit(EXIT_DIGEST_MISMATCH)
+    if not args.full:
+        return out
     hb.phase('allreduce_alone')
     share = getattr(args, 'share_gpu', False)
     ms, bus, nbytes = bare_allreduce(job, pg, world, iters=2 if share else 5, warm=1 if share else 2)
@@ -1123,7 +1180,7 @@ def dry_run(args, rank, world):
                               if k in extra or k.startswith('route_') or k == 'supervised'})
         save_main_line(res)
     hb.phase('main_done')
-    if pg is not None and not args.no_route_ab:
+    if pg is not None and args.full and not args.no_route_ab:
         legs = route_ab(job, pg, rank, world, args.steps, hb, 1)
         if rank == 0:
             res.update(legs)
@@ -1249,6 +1306,9 @@ def main():
     eng.reducer.log = None
     out = job.last
     probe0 = [job.first_probe]
+    if rank == 0 and args.dump_outputs:
+        # before anything else runs on this engine: the extras below take more steps
+        dump_outputs(args.dump_outputs, train_outputs(eng, out))
     if pg is not None:
         check_rank_digests(job, pg, rank, world, hb, 'after the timed steps')
     hb.phase('extras')
@@ -1261,7 +1321,7 @@ def main():
     # wgrad and update - the one every rank of an N > 1 job takes - so that a scaling series can be
     # read against a like-for-like N = 1 number (reported beside `value`, never as `value`).
     deferred_ms = None
-    if world == 1 and not args.no_fused_update and eng._can_fuse_wgrad_update():
+    if args.full and world == 1 and not args.no_fused_update and eng._can_fuse_wgrad_update():
         eng.timing_events = eng.phase_events = eng.update_events = eng.comm_events = None
         n_def = args.steps               # the same number of steps as `value`
         for it in range(5 + n_def):
@@ -1277,8 +1337,8 @@ def main():
     # One rank: what the N-rank schedule costs THIS GPU when something occupies compute units and
     # HBM the way the RCCL exchange would (reducer.EmulatedExchange; a projection, labelled so)
     projections = {}
-    if world == 1 and args.mfma_dtype == 'fp16x2' and not args.share_gpu and not args.force_dist \
-            and not args.no_projection:
+    if args.full and world == 1 and args.mfma_dtype == 'fp16x2' and not args.share_gpu \
+            and not args.force_dist and not args.no_projection:
         spec = [x for x in args.emulate_exchange.split(',') if x]
         # Two paces per rank count: the links delivering 0.6 of their
         # 153 GB/s per direction (the optimistic point of rounds 4-5) and 0.3 of it (RCCL's bus
@@ -1299,7 +1359,7 @@ def main():
                                                                         psteps, sharded=True)
     conv_alone_ms = None
     roipool_alone_ms = None
-    if rank == 0:
+    if args.full and rank == 0:
         eng.timing_events = eng.phase_events = eng.update_events = eng.comm_events = None
         eng.conv_body(t['data'])
         torch.cuda.synchronize()
@@ -1555,9 +1615,11 @@ def main():
         # fc6_w's gradient, exchanges it and updates in the deferred kernel, while `value` at
         # N = 1 updates fc6_w inside its wgrad GEMM.  This field is the N = 1 point of the N > 1
         # ALGORITHM (same steps, same clock as `value`); at N > 1 it equals `value`.
-        res['scaling_baseline_value'] = (round(world * B / deferred_ms * 1e3, 3)
-                                         if deferred_ms is not None else res['value'])
-        if world == 1 and args.mfma_dtype == 'fp16x2' and not args.no_alt_plan:
+        if deferred_ms is not None:
+            res['scaling_baseline_value'] = round(world * B / deferred_ms * 1e3, 3)
+        elif world > 1 or args.full:
+            res['scaling_baseline_value'] = res['value']
+        if args.full and world == 1 and args.mfma_dtype == 'fp16x2' and not args.no_alt_plan:
             # the same workload, measured in this run, (a) with the exact 3 x bf16 operand split
             # and (b) with every GEMM on v_mfma_f32_32x32x2_f32, for readers who want the number
             # without the 2 x f16 operand representation
@@ -1581,7 +1643,7 @@ def main():
                 res[key].pop('probe', None)
             if not args.no_extra_configs and headline and B == 2:
                 extra_configs(args, dev, B, res, cfg, roof)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(args, num_fg)
         # N > 1 (or --force-dist): the broadcast / bare-exchange / rank-digest keys, flat in the
         # line and in config (the driver's parser keeps flat keys), and what the supervisor did
@@ -1591,7 +1653,7 @@ def main():
         cfg.update(fallback_keys())
         save_main_line(res)
     hb.phase('main_done')
-    if pg is not None and not args.no_route_ab and args.mfma_dtype == 'fp16x2':
+    if pg is not None and args.full and not args.no_route_ab and args.mfma_dtype == 'fp16x2':
         # the other update routes, K steps each, in this same job (value stays the default route's)
         job.timed_hooks = None
         legs = route_ab(job, pg, rank, world, args.steps, hb, B)

@@ -53,7 +53,7 @@ def main():
     lines = ["# PMC reading of the default plan's kernels inside `bench.py`", '',
              '`rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES '
              'SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE -- python '
-             'bench.py --no-cpu-baseline --no-alt-plan --steps 3 --warmup 1`',
+             'bench.py --full --no-cpu-baseline --no-alt-plan --steps 3 --warmup 1`',
              '(one counter pass, `na-fwebsod_amd/tools/profile_bench.sh`; under counter collection kernels are '
              'serialised, so durations are 5-12 % above the un-profiled ones and concurrent streams do not '
              'overlap).', '',

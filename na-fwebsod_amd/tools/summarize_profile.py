@@ -154,7 +154,7 @@ def summarize(stats_dir, fetch_dir, write_dir, out, mode='fp16x2', require_domin
             'WRITE_SIZE_KiB_per_launch': dom['WRITE_SIZE'],
             'hbm_bytes_per_launch': tb,
             'ratio_vs_algorithmic': round(tb / (alg_gb * 1e9), 3),
-            'note': 'separate --pmc passes of `bench.py --steps 2 --warmup 1`; read bytes = '
+            'note': 'separate --pmc passes of `bench.py --full --steps 2 --warmup 1`; read bytes = '
                     '2*FETCH_SIZE*1024 (gfx950 FETCH_SIZE counts 64 B per 128-B request; '
                     'Infinity-Cache hits are included in the memory-side counters)'}
         lines += ['', 'fc6 fwd GEMM: FETCH %.0f KiB, WRITE %.0f KiB per launch -> %.2f GB fabric '

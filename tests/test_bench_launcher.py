@@ -92,7 +92,7 @@ def _line(r):
 
 
 def test_two_ranks_broadcast_digest_bare_exchange_and_route_ab():
-    r = _run('--gpus', '2', '--dry-run', '--steps', '6', '--warmup', '2')
+    r = _run('--gpus', '2', '--dry-run', '--full', '--steps', '6', '--warmup', '2')
     assert r.returncode == 0, r.stderr[-3000:]
     res = _line(r)
     # (d) the ranks are seeded differently: only the broadcast from rank 0 makes them equal
@@ -115,7 +115,7 @@ def test_two_ranks_broadcast_digest_bare_exchange_and_route_ab():
 
 
 def test_three_ranks_cannot_shard_and_say_so():
-    r = _run('--gpus', '3', '--dry-run', '--steps', '3', '--warmup', '1')
+    r = _run('--gpus', '3', '--dry-run', '--full', '--steps', '3', '--warmup', '1')
     assert r.returncode == 0, r.stderr[-3000:]
     res = _line(r)
     assert res['value_sharded'] is None and 'do not divide' in res['sharded_skipped']
@@ -125,7 +125,7 @@ def test_three_ranks_cannot_shard_and_say_so():
 def test_a_stall_on_the_pipelined_route_falls_back_to_fresh_unpipelined_workers():
     """(e): rank 1 stops inside the timed steps of the pipelined route; every rank's supervisor
     kills its worker and starts a FRESH one with --no-pipeline-update; the line says so."""
-    r = _run('--gpus', '2', '--dry-run', '--steps', '4', '--warmup', '1',
+    r = _run('--gpus', '2', '--dry-run', '--full', '--steps', '4', '--warmup', '1',
              env=dict(FAST, NAWS_BENCH_INJECT='stall:pipelined:1:1'))
     assert r.returncode == 0, r.stderr[-3000:]
     res = _line(r)
@@ -164,7 +164,7 @@ def test_diverging_ranks_exit_with_the_digest_code_and_fall_back():
 
 
 def test_a_stall_in_an_ab_leg_keeps_the_headline():
-    r = _run('--gpus', '2', '--dry-run', '--steps', '3', '--warmup', '1',
+    r = _run('--gpus', '2', '--dry-run', '--full', '--steps', '3', '--warmup', '1',
              env=dict(FAST, NAWS_BENCH_INJECT='stall:sharded:0'))
     assert r.returncode == 0, r.stderr[-3000:]
     res = _line(r)
@@ -191,3 +191,33 @@ def test_supervisor_ladder_and_deadlines():
     assert sv.deadline_of(dict(phase='timed', steps=20), scale=0.5) == 55.0
     assert sv.deadline_of(dict(phase='???')) == 300.0
     assert sv.last_heartbeat('/nonexistent/hb', 12.5) == dict(phase='boot', t=12.5, steps=0)
+
+
+def test_a_plain_n_rank_run_leaves_the_bare_exchange_and_route_ab_to_full():
+    r = _run('--gpus', '2', '--dry-run', '--steps', '3', '--warmup', '1')
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = _line(r)
+    assert res['steps'] == 3 and res['ms_per_step'] > 0
+    assert res['params_broadcast_from_rank0'] is True and res['rank_digest_equal'] is True
+    assert 'allreduce_alone_ms' not in res
+    assert not any(k.startswith('value_') for k in res)
+
+
+def test_dump_outputs_writes_float32_npy_and_keeps_to_the_limit(tmp_path):
+    import numpy as np
+    d = str(tmp_path / 'out')
+    bench.dump_outputs(d, {'a': np.arange(6, dtype=np.int32).reshape(2, 3),
+                           'b': np.ones(4, np.float16), 'c': np.zeros(2, np.float64)})
+    assert sorted(os.listdir(d)) == ['a.npy', 'b.npy', 'c.npy']
+    a = np.load(os.path.join(d, 'a.npy'))
+    assert a.dtype == np.float32 and a.shape == (2, 3) and a[1, 2] == 5
+    assert np.load(os.path.join(d, 'b.npy')).dtype == np.float32
+    assert np.load(os.path.join(d, 'c.npy')).dtype == np.float64
+    big = np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)
+    try:
+        bench.dump_outputs(str(tmp_path / 'big'), {'x': big})
+    except SystemExit as e:
+        assert 'dump limit' in str(e)
+    else:
+        raise AssertionError('a dump above the limit was written')
+    assert not os.path.exists(str(tmp_path / 'big'))

@@ -31,37 +31,31 @@ def test_box_helpers_match_reference():
     assert np.allclose(B.crowd_iou(np.array([[0, 0, 10, 10.]]), np.array([[5, 0, 10, 10.]])), 0.5)
 
 
-def _ref_cython_bbox():
-    """The reference's own cython_bbox.pyx, compiled where it lies by `make -C oracle ref`
-    (oracle/_ref/, git-ignored, travels with gpurun); None when it has not been built."""
-    import glob
-    import importlib.util
-    so = glob.glob(os.path.join(ROOT, 'oracle', '_ref', 'cython_bbox*.so'))
-    if not so:
-        return None
-    spec = importlib.util.spec_from_file_location('cython_bbox', so[0])
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+def fresh_box_pairs():
+    """(n, k, boxes, query) on which tests/golden/make_golden_bbox_overlaps.py recorded the
+    reference's compiled cython_bbox.bbox_overlaps (reference_bbox_overlaps.npz, fresh_<n>x<k>)."""
+    rng = np.random.default_rng(23)
+    out = []
+    for n, k in ((1, 1), (57, 9), (300, 40)):
+        b = rng.uniform(0, 500, (n, 4)).astype(np.float32)
+        b[:, 2:] += b[:, :2]
+        q = rng.uniform(0, 500, (k, 4)).astype(np.float32)
+        q[:, 2:] += q[:, :2]
+        out.append((n, k, b, q))
+    return out
 
 
 def test_bbox_overlaps_and_proposal_merge_match_reference(cfgmod):
     """bbox_overlaps (numpy restatement) against the golden produced by the COMPILED reference
-    cython_bbox, and - when oracle/_ref is built - against that module live on fresh boxes;
+    cython_bbox, and against that module's results on fresh boxes (reference_bbox_overlaps.npz);
     _merge_proposal_boxes_into_roidb against the reference function run on top of it."""
     cfgmod.merge_cfg_from_file(YAML)
     from detectron.utils import boxes as B
     from detectron.datasets import json_dataset_wsl as jd
     assert np.array_equal(B.bbox_overlaps(G['bo_boxes'], G['bo_query']), G['bo_out'])
-    ref = _ref_cython_bbox()
-    if ref is not None:
-        rng = np.random.default_rng(23)
-        for n, k in ((1, 1), (57, 9), (300, 40)):
-            b = rng.uniform(0, 500, (n, 4)).astype(np.float32)
-            b[:, 2:] += b[:, :2]
-            q = rng.uniform(0, 500, (k, 4)).astype(np.float32)
-            q[:, 2:] += q[:, :2]
-            assert np.array_equal(B.bbox_overlaps(b, q), ref.bbox_overlaps(b, q))
+    ref = np.load(os.path.join(ROOT, 'tests', 'golden', 'reference_bbox_overlaps.npz'))
+    for n, k, b, q in fresh_box_pairs():
+        assert np.array_equal(B.bbox_overlaps(b, q), ref['fresh_%dx%d' % (n, k)])
     rng = np.random.default_rng(17)   # unused draws keep nothing in sync: inputs come from the golden
     gtb = G['mg_boxes'][:6]
     e = dict(boxes=gtb.copy(), obn_scores=np.zeros((6, 1), np.float32),

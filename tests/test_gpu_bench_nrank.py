@@ -32,7 +32,7 @@ def _bench(*argv, env=None, timeout=840):
 
 
 def test_two_ranks_on_one_gpu_broadcast_digests_bare_exchange_and_route_ab(dev):
-    r, res = _bench('--gpus', '2', '--share-gpu', *SMALL)
+    r, res = _bench('--gpus', '2', '--share-gpu', '--full', *SMALL)
     assert r.returncode == 0 and res is not None, r.stderr[-4000:]
     assert res['n_gpus'] == 2 and res['config']['shared_gpu'] is True
     assert res['supervised'] is True and res['route_fallback'] is None and res['route_attempt'] == 0
@@ -65,7 +65,7 @@ def test_one_rank_over_rccl_executes_every_routes_collectives(dev):
     """--force-dist: world 1 on the nccl backend.  The all-reduce route's chunked messages with
     per-message waits from the update stream (pipelined), the one-launch route, and the sharded
     route's dist.reduce + all_gather_into_tensor legs all execute on RCCL."""
-    r, res = _bench('--gpus', '1', '--force-dist', *SMALL)
+    r, res = _bench('--gpus', '1', '--force-dist', '--full', *SMALL)
     assert r.returncode == 0 and res is not None, r.stderr[-4000:]
     assert res['config']['rccl_backend'] == 'nccl' and res['config']['rccl_world_size'] == 1
     assert res['rank_digest_equal'] is True and res['params_broadcast_from_rank0'] is True

@@ -243,14 +243,12 @@ def test_missing_weights_file_is_an_error(cfgmod, tmp_path):
     assert not any(f.endswith('.pkl') for _d, _s, fs in os.walk(str(tmp_path)) for f in fs)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/detectron'),
-                    reason='needs the imported reference (build container only)')
 def test_imported_reference_config_merges_the_dumped_cfg(cfgmod, tmp_path):
     """The `cfg` string of a detections.pkl written here goes through the REFERENCE's own
-    load_cfg + merge_cfg_from_cfg (what tools/reval.py:88-93 does) in a child interpreter (the
-    two packages share the name `detectron`): no unknown key, no type error, and the values
-    that steer the reader come out as written."""
-    import subprocess
+    load_cfg + merge_cfg_from_cfg (what tools/reval.py:88-93 does) without an unknown key or a type
+    error, and the values that steer the reader come out as written.  The reference's verdict is
+    recorded in tests/golden/reference_cfg_load.json (make_golden_cfg_load.py runs the imported
+    reference on this very dump): the string written here must still be the recorded one."""
     from detectron.core import test_engine_wsl as te
     _cfg(cfgmod, tmp_path, 2, 1)
     ab, asg, akp = te.empty_results(4, 2)
@@ -262,35 +260,15 @@ def test_imported_reference_config_merges_the_dumped_cfg(cfgmod, tmp_path):
     from detectron.utils.net_wsl import save_object
     wf = str(tmp_path / 'model_final.pkl')
     save_object(dict(blobs={}, cfg=envu.yaml_dump(cfg, reference_format=True)), wf)
-    script = textwrap.dedent('''
-        import pickle, sys
-        sys.dont_write_bytecode = True
-        sys.path.insert(0, %r)
-        import yaml
-        from make_golden_from_reference import REF, _StubFinder
-        sys.meta_path.insert(0, _StubFinder())
-        sys.path.insert(0, REF)
-        import future.utils
-        future.utils.iteritems = lambda d: iter(d.items())
-        import detectron.utils.env as envu
-        # (the reference's `yaml.load` without a Loader argument is PyYAML's unsafe loader)
-        envu.yaml_load = lambda s: yaml.load(s, Loader=yaml.UnsafeLoader)
-        from detectron.core import config as rcfg
-        assert rcfg.__file__.startswith(REF)
-        dets = pickle.load(open(%r, 'rb'))
-        rcfg.merge_cfg_from_cfg(rcfg.load_cfg(dets['cfg']))
-        c = rcfg.cfg
-        print('MERGED', c.MODEL.NUM_CLASSES, c.TEST.BBOX_AUG.ENABLED, type(c.TEST.BBOX_AUG.SCALES).__name__,
-              c.PIXEL_MEANS.shape, len(dets['all_boxes']), len(dets['all_segms'][1]))
-        # a weights file written here, read the reference's way (utils/net_wsl.py:64-66, :277)
-        saved = rcfg.load_cfg(pickle.load(open(%r, 'rb'))['cfg'])
-        print('WEIGHTS_CFG', type(saved).__name__, 'MODEL' in saved, 'BBOX_REG_WEIGHTS' in saved.MODEL,
-              saved.MODEL.TYPE, saved.WSL.DILATION)
-    ''') % (os.path.join(ROOT, 'tests', 'golden'), f, wf)
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
-    env.pop('PYTHONPATH', None)
-    r = subprocess.run([sys.executable, '-c', script], capture_output=True, text=True, env=env,
-                       cwd=str(tmp_path))
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert 'MERGED 4 %s tuple (1, 1, 3) 4 2' % cfg.TEST.BBOX_AUG.ENABLED in r.stdout, r.stdout
-    assert 'WEIGHTS_CFG AttrDict True True generalized_wsl 2' in r.stdout, r.stdout
+    gold = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'reference_cfg_load.json')))
+    dets = pickle.load(open(f, 'rb'))
+    assert len(dets['all_boxes']) == 4 and len(dets['all_segms'][1]) == 2
+    for path in (f, wf):
+        s = pickle.load(open(path, 'rb'))['cfg'].replace(str(tmp_path), gold['output_dir_placeholder'])
+        s = s.replace(ROOT, gold['root_dir_placeholder'])
+        assert s == gold['cfg'], ('%s: the dumped cfg is not the one the reference was run on '
+                                  '(re-record with tests/golden/make_golden_cfg_load.py)' % path)
+    assert gold['bbox_aug_enabled'] == bool(cfg.TEST.BBOX_AUG.ENABLED)
+    out = '\n'.join(gold['reference_stdout'])
+    assert 'MERGED 4 %s tuple (1, 1, 3) 4 2' % cfg.TEST.BBOX_AUG.ENABLED in out, out
+    assert 'WEIGHTS_CFG AttrDict True True generalized_wsl 2' in out, out

@@ -23,6 +23,7 @@ Blob names, shapes and update rule follow the reference:
   detectron/ops/acm_weightdecay_momentum_sgd_op.h:48-112.
 """
 
+import collections
 import os
 
 import numpy as np
@@ -40,6 +41,84 @@ VGG16_CONVS = [
     ('conv4_1', 256, 512, 1), ('conv4_2', 512, 512, 1), ('conv4_3', 512, 512, 1), ('pool4',),
     ('conv5_1', 512, 512, None), ('conv5_2', 512, 512, None), ('conv5_3', 512, 512, None),
 ]
+
+# The entries of conv_plan().  form: c3 (conv1_1: three input channels, NCHW in); h2_direct,
+# h2_wino2, h2_wino4 (fp16x2: the direct halo-tile kernel, Winograd F(2x2,3x3), F(4x4,3x3));
+# x3_direct, x3_wino (fp32x3: 3 x bf16 weight planes); f32_direct, f32_wino (fp32); bf16_wp (the
+# wave-private halo-tile kernel on one bf16 plane).  direct_alt: the layer also carries h2_direct,
+# taken per input size (DIRECT_MIN_TILES); pool2: the 2x2 / stride-2 max-pool that follows may be
+# taken in the direct kernel's epilogue; weight_bound: the layer hands the next one an upper bound
+# of max|y| from its weights.
+ConvStep = collections.namedtuple('ConvStep',
+                                  'name form cin cout dilation direct_alt pool2 weight_bound')
+PoolStep = collections.namedtuple('PoolStep', 'form stride')          # form 'pool'
+_H2_FORMS = ('h2_direct', 'h2_wino2', 'h2_wino4')
+
+
+def conv_plan(mfma_dtype, dilation, wino_f4_min_cin):
+    """The form of every VGG16_CONVS entry (a ConvStep or PoolStep each) under the arithmetic plan
+    `mfma_dtype`; dilation: the engine's (2: conv5_x dilated behind a stride-1 pool4)."""
+    if mfma_dtype not in ('fp32', 'fp32x3', 'fp16x2', 'bf16'):
+        raise ValueError('unknown mfma_dtype %r' % (mfma_dtype,))
+    plan = []
+    for i, item in enumerate(VGG16_CONVS):
+        if item[0].startswith('pool'):
+            plan.append(PoolStep('pool', item[1] if len(item) > 1 else 1 if dilation == 2 else 2))
+            continue
+        name, cin, cout, dil = item
+        wino = cin >= 128 and cout >= 256          # conv3_1 .. conv5_3
+        if name == 'conv1_1':
+            form = 'c3'
+        elif mfma_dtype == 'bf16':
+            form = 'bf16_wp'
+        elif mfma_dtype == 'fp32':
+            form = 'f32_wino' if wino else 'f32_direct'
+        elif mfma_dtype == 'fp32x3':
+            # conv3_x: the 3-plane direct kernel fills the chip there
+            form = 'x3_wino' if wino and cout > 256 else 'x3_direct'
+        elif not wino:
+            form = 'h2_direct'
+        elif 0 < wino_f4_min_cin <= cin and cout >= 512:
+            # (conv3_2 / conv3_3, 256 -> 256 at 150 x 250, stay off F(4x4): their V and M are 88 MB
+            # each way for a quarter of conv4_2's products - 0.24 vs 0.19 ms per layer-image inside
+            # a step)
+            form = 'h2_wino4'
+        else:
+            form = 'h2_wino2'
+        # (F(4x4) layers never switch to the direct form: 42.4 vs 43.5 ms per TTA image with it
+        # taking over at the large scales, 44.5 for F(2x2) with it)
+        direct_alt = form == 'h2_wino2'
+        pool2 = (i + 1 < len(VGG16_CONVS) and VGG16_CONVS[i + 1][0] == 'pool'
+                 and (direct_alt or form in ('h2_direct', 'x3_direct', 'bf16_wp')))
+        plan.append(ConvStep(name, form, cin, cout, dil or (2 if dilation == 2 else 1), direct_alt,
+                             pool2, form == 'c3' and mfma_dtype == 'fp16x2'))
+    return plan
+
+
+def _conv_operand(form, w):
+    """The weight operand of a layer run in `form`, from its fp32 OIHW weight: the packed weight
+    [Cout][9 Cin] or U [16 | 36][Cout][Cin], split into 16-bit planes unless the form is fp32."""
+    if form == 'c3':
+        return w
+    if form == 'h2_wino4':
+        m = ops.winograd4_weight_transform(w)
+    elif 'wino' in form:
+        m = ops.winograd_weight_transform(w)
+    else:
+        m = ops.conv3x3_pack_weight(w).view(w.shape[0], -1)
+    if form.startswith('f32'):
+        return m
+    split = {'h2': ops.split_f16x2, 'x3': ops.split_bf16x3, 'bf16': ops.to_bf16_slab}
+    return split[form.split('_')[0]](m)
+
+
+# An entry packed by set_conv_blobs: the step and, for a conv, the fp32 weight and bias, its form's
+# operand, the direct form's (direct_alt) and the (mul, add) of its weight bound (weight_bound)
+ConvLayer = collections.namedtuple('ConvLayer', 'step w b operand direct affine')
+# What a conv chain carries between layers: the activation, the int32 word of an upper bound of
+# max|x| (or None), the (mul, add) to apply to it, and whether the pool that follows is done
+ChainState = collections.namedtuple('ChainState', 'x bound affine pooled')
+_IDENTITY = (1.0, 0.0)
 
 HIDDEN = 4096
 
@@ -218,7 +297,7 @@ class WsddnEngine(object):
         self._lr_host = 0.0
         self.sgd_iter_count = 0      # the SGD op's iter_count_ state
         self.step_count = 0          # forward/backward passes run (dropout stream)
-        self.conv = {}               # name -> (weight (OIHW or packed), bias)
+        self.conv_layers = []        # one ConvLayer per VGG16_CONVS entry (set_conv_blobs)
         self.stat_state = None
         # ---- the public toggles (everything else about the plan is fixed; the arms that lost
         # their A/B are gone - docs/history/ has each measurement) ---------------------------------
@@ -248,17 +327,17 @@ class WsddnEngine(object):
         # least this many input channels (256: conv4_1..conv5_3; 512 leaves conv4_1 to F(2x2)'s
         # fused kernel: conv body 2.099 vs 2.082 ms, tools/ab_wino4.py); 0 = F(2x2) everywhere
         self.WINO_F4_MIN_CIN = 256
-        # fp32x3: up to this many output channels the direct 3-plane kernel, Winograd above
-        self.X3_DIRECT_MAX_COUT = 256
         # fc8's products (tiny output, long K): K in 4 slices + a deterministic second pass (58 vs
         # 97 us, tools/bench_fc8.py)
         self.FC8_KSPLIT = 4
         # entries of VGG16_CONVS each image runs before the deferred update is queued beside the
-        # chains (1: conv1_1; 2: conv1_1 + conv1_2 with pool1)
+        # chains (1: conv1_1; 2: conv1_1 + conv1_2 with pool1); fp32 / fp32x3 queue it before them
         self.UPDATE_AFTER = 2 if mfma_dtype == 'bf16' else 1
+        self._update_behind_heads = mfma_dtype in ('fp16x2', 'bf16')
         # fp16x2 plan: each image's proposals are pooled on that image's conv stream (conv_body)
         self.ROI_POOL_ON_CHAINS = True
-        self.conv_wino = {}
+        # the 16-bit plans' RoIPoolF reads block-maxima maps of conv5_3, built beside the chains
+        self._roi_maps_on_chains = mfma_dtype in ('fp16x2', 'bf16')
         self._rm_table = None
         self._fc8_ws = None
         self._w6_updated = None      # the region table for the deferred kernel once fc6_w is done
@@ -266,7 +345,6 @@ class WsddnEngine(object):
         self._sgd_regions = None
         self._seg_ring = None
         self._amax5 = None
-        self.conv_direct_h2 = {}
         self._streams = []
         self._update_pending = False
         self._update_waiting = False
@@ -383,56 +461,27 @@ class WsddnEngine(object):
         return self.arena.view(self.momentum_buf, name)
 
     def set_conv_blobs(self, blobs):
-        """blobs: name_w [O,I,3,3], name_b [O] (reference layout).  Packs once."""
-        for item in VGG16_CONVS:
-            if item[0].startswith('pool'):
+        """blobs: name_w [O,I,3,3], name_b [O] (reference layout).  Packs each layer once, for the
+        form conv_plan() gives it."""
+        layers = []
+        for s in conv_plan(self.mfma_dtype, self.dilation, self.WINO_F4_MIN_CIN):
+            if s.form == 'pool':
+                layers.append(ConvLayer(s, None, None, None, None, None))
                 continue
-            name, dil = item[0], item[3]
-            w = blobs[name + '_w'].to(self.device, torch.float32).contiguous()
-            b = blobs[name + '_b'].to(self.device, torch.float32).contiguous()
-            use_wino = (self.mfma_dtype != 'bf16' and w.shape[1] >= 128 and w.shape[0] >= 256)
-            if self.mfma_dtype == 'fp32x3' and w.shape[0] <= self.X3_DIRECT_MAX_COUT:
-                use_wino = False          # conv3_x: the 3-plane direct kernel fills the chip there
-            x3conv = (self.mfma_dtype in ('fp32x3', 'fp16x2') and name != 'conv1_1' and not use_wino)
-            if name == 'conv1_1':
-                packed = w
-                # |conv1_1(x)| <= max|x| * max_c sum|w_c| + max|b|: the operand-scale bound of
-                # the layer that consumes it, without a pass over its 154 MB output
-                self._c11_bound = (float(w.abs().sum(dim=(1, 2, 3)).max().item()),
-                                   float(b.abs().max().item()))
-            elif (x3conv and self.mfma_dtype == 'fp16x2' and dil == 1
-                  and w.shape[0] <= 128 and w.shape[0] % 32 == 0 and w.shape[1] % 16 == 0):
-                # f16 hi / lo planes [2][9*Cin/16][Cout][16] + per-channel scales
-                packed = ops.split_f16x2(ops.conv3x3_pack_weight(w).view(w.shape[0], -1))
-            elif x3conv:
-                # weight planes [3][9*Cin/16][Cout][16] of the packed [Cout][3][3][Cin] weight
-                packed = ops.split_bf16x3(ops.conv3x3_pack_weight(w).view(w.shape[0], -1))
-            elif use_wino:
-                # (conv3_2 / conv3_3, 256 -> 256 at 150 x 250, stay on the direct kernel: as F(4x4)
-                # their V and M are 88 MB each way for a quarter of conv4_2's products - 0.24 vs
-                # 0.19 ms per layer-image inside a step)
-                f4 = (self.mfma_dtype == 'fp16x2' and 0 < self.WINO_F4_MIN_CIN <= w.shape[1]
-                      and w.shape[1] % 32 == 0 and w.shape[0] >= 512)
-                packed = (ops.winograd4_weight_transform(w) if f4          # [36][Cout][Cin]
-                          else ops.winograd_weight_transform(w))           # [16][Cout][Cin]
-                if self.mfma_dtype == 'fp16x2':
-                    packed = ops.split_f16x2(packed)           # F16x2, planes [2][16][Cin/16][Cout][16]
-                    # (F(4x4) layers never switch: 42.4 vs 43.5 ms per TTA image with the direct
-                    # form taking over at the large scales, 44.5 for F(2x2) with it)
-                    if not f4 and w.shape[0] % 128 == 0 and \
-                            (dil == 1 or (dil is None and self.dilation in (1, 2))):
-                        # also the direct form: chosen per input size in _conv_chain
-                        self.conv_direct_h2[name] = ops.split_f16x2(
-                            ops.conv3x3_pack_weight(w).view(w.shape[0], -1))
-                elif self.mfma_dtype == 'fp32x3':
-                    packed = ops.split_bf16x3(packed)          # planes [3][16][Cin/16][Cout][16]
-            elif self.mfma_dtype == 'bf16' and w.shape[0] % 64 == 0 and w.shape[1] % 64 == 0:
-                # one bf16 plane [9*Cin/16][Cout][16]: the wave-private halo-tile kernel
-                packed = ops.to_bf16_slab(ops.conv3x3_pack_weight(w).view(w.shape[0], -1))
-            else:
-                packed = ops.conv3x3_pack_weight(w)            # [Cout][3][3][Cin]
-            self.conv[name] = (packed, b, w)
-            self.conv_wino[name] = use_wino
+            for key, shape in ((s.name + '_w', (s.cout, s.cin, 3, 3)), (s.name + '_b', (s.cout,))):
+                if tuple(blobs[key].shape) != shape:
+                    raise ValueError('%s has shape %s, the layer needs %s'
+                                     % (key, tuple(blobs[key].shape), shape))
+            w = blobs[s.name + '_w'].to(self.device, torch.float32).contiguous()
+            b = blobs[s.name + '_b'].to(self.device, torch.float32).contiguous()
+            # |conv1_1(x)| <= max|x| * max_c sum|w_c| + max|b|: the operand-scale bound of the
+            # layer that consumes it, without a pass over its 154 MB output
+            affine = ((float(w.abs().sum(dim=(1, 2, 3)).max().item()), float(b.abs().max().item()))
+                      if s.weight_bound else None)
+            operand = _conv_operand(s.form, w)
+            direct = _conv_operand('h2_direct', w) if s.direct_alt else None
+            layers.append(ConvLayer(s, w, b, operand, direct, affine))
+        self.conv_layers = layers
 
     def set_head_blobs(self, blobs):
         for name, shape in self.arena.specs:
@@ -451,10 +500,11 @@ class WsddnEngine(object):
         root = dist.get_global_rank(self.pg, src)
         dist.broadcast(self.params, root, group=self.pg)
         dist.broadcast(self.momentum_buf, root, group=self.pg)
-        if self.conv:
-            for _wp, b, w in self.conv.values():
-                dist.broadcast(w, root, group=self.pg)
-                dist.broadcast(b, root, group=self.pg)
+        if self.conv_layers:
+            for lay in self.conv_layers:
+                if lay.w is not None:
+                    dist.broadcast(lay.w, root, group=self.pg)
+                    dist.broadcast(lay.b, root, group=self.pg)
             self.set_conv_blobs({k: v for k, v in self.export_blobs(False).items()
                                  if k.startswith('conv')})
         # self.params was written directly: the operand planes no longer match it
@@ -496,8 +546,9 @@ class WsddnEngine(object):
             raise RuntimeError('NAWS.SHARDED_UPDATE: fc6_w momentum rows live with their owners; '
                                'call gather_sharded_state() on EVERY rank before a checkpoint')
         out = {}
-        for name, (wp, b, w) in self.conv.items():
-            out[name + '_w'], out[name + '_b'] = w, b
+        for lay in self.conv_layers:
+            if lay.w is not None:
+                out[lay.step.name + '_w'], out[lay.step.name + '_b'] = lay.w, lay.b
         for name, _ in self.arena.specs:
             out[name] = self.blob_ro(name)
             if with_momentum:
@@ -505,101 +556,65 @@ class WsddnEngine(object):
         return out
 
     # ---------------------------------------------------------------- forward
-    def _conv_chain(self, data, out=None, amax_final=None, first=0, end=None, x=None,
-                    bound_in=None, amax_last=None, affine_in=None):
-        """data NCHW [b,3,H,W] -> conv5_3 NHWC, on the current stream.  amax_final (int32 [1],
-        fp16x2 plan): receives the bit pattern of max|conv5_3| for the RoIPool operand scale.
-        first / end: run only VGG16_CONVS[first:end] (x = the input of layer `first`, bound_in = the
-        word holding an upper bound of max|x|); amax_last: a pre-zeroed word that the LAST layer of
-        the range max-es its max|y| into (shared by the per-image chains)."""
-        last = VGG16_CONVS[-1][0]
-        end = len(VGG16_CONVS) if end is None else end
-        # fp16x2 Winograd layers hand max|y| to the next layer (its operand scale needs an upper
-        # bound of max|x|; a max-pool in between only lowers it), saving that layer's own pass
-        amax = (torch.zeros((len(VGG16_CONVS) + 1,), device=self.device, dtype=torch.int32)   # one fill
-                if self.mfma_dtype == 'fp16x2' else None)
-        prev, affine = None, (1.0, 0.0)  # slot holding the bound for the current x, if any
-        if bound_in is not None:         # (affine_in: the bound is bound_in * mul + add, once)
-            amax[-1:].copy_(bound_in)
-            prev = len(VGG16_CONVS)
-            if affine_in is not None:
-                affine = affine_in
-        affine_slot = 0 if affine_in is None else len(VGG16_CONVS)
-        fused_pool = False               # the previous layer's epilogue already pooled
-        last_conv = max(i for i in range(first, end) if not VGG16_CONVS[i][0].startswith('pool'))
-        for li, item in enumerate(VGG16_CONVS):
-            if li < first or li >= end:
+    def _conv_chain(self, layers, st, out=None, amax_out=None):
+        """Run `layers` (a slice of self.conv_layers) on the current stream from ChainState `st`;
+        returns the state after them.  The last layer of the slice writes into `out` and, fp16x2
+        plan, max|y| into the int32 word `amax_out` (conv5_3: fc6's RoIPool operand scale).
+
+        fp16x2 layers hand max|y| to the next layer (its operand scale needs an upper bound of
+        max|x|; a max-pool in between only lowers it), saving that layer's own pass; the words
+        the direct kernel max-es into are zeroed by one fill per call."""
+        x, bound, aff, pooled = st
+        words = (torch.zeros((len(layers),), device=self.device, dtype=torch.int32)
+                 if any(lay.step.form in _H2_FORMS for lay in layers) else None)
+        for k, lay in enumerate(layers):
+            s = lay.step
+            if s.form == 'pool':
+                if not pooled:
+                    x = ops.maxpool2x2_nhwc(x, s.stride)
+                pooled = False
                 continue
-            if item[0] == 'pool':
-                if not fused_pool and not (li == first and self._pool_done):
-                    x = ops.maxpool2x2_nhwc(x, 2)
-                fused_pool = False
-            elif item[0] == 'pool4':
-                x = ops.maxpool2x2_nhwc(x, 1 if self.dilation == 2 else 2)
-            else:
-                name, _, _, dil = item
-                wp, b, _w = self.conv[name]
-                if name == 'conv1_1':
-                    x = ops.conv3x3_c3_nchw_to_nhwc(data, wp, b, True)
-                    prev = None
-                    if self.mfma_dtype == 'fp16x2':
-                        ops.amax_word(data, out=amax[li:li + 1])     # 7 MB: the network input
-                        prev, affine = li, self._c11_bound
-                else:
-                    d = dil if dil is not None else (2 if self.dilation == 2 else 1)
-                    dst = out if name == last else None
-                    wd = self.conv_direct_h2.get(name)
-                    if wd is not None and d in (1, 2):
-                        # direct 2 x f16 halo-tile kernel where it fills the chip (>= one 8x32-pixel
-                        # x 128-channel tile per CU: conv3_x at 600x1000, and every deep layer once
-                        # the images share a launch), Winograd below that
-                        tiles = x.shape[0] * ((x.shape[1] + 7) // 8) * ((x.shape[2] + 31) // 32)
-                        if tiles * (wd.planes.shape[-2] // 128) >= self.DIRECT_MIN_TILES:
-                            wp = wd
-                    if isinstance(wp, ops.F16x2):
-                        bound = None if prev is None else amax[prev:prev + 1]
-                        word = amax_final if (name == last and amax_final is not None) \
-                            else amax[li:li + 1]
-                        zeroed = word is not amax_final
-                        if li == last_conv and amax_last is not None:
-                            word, zeroed = amax_last, True
-                        if wp.planes.dim() == 4:         # direct halo-tile kernel
-                            mul, add = affine if prev == affine_slot else (1.0, 0.0)
-                            # a 2x2 / stride-2 max-pool that follows is taken in the epilogue
-                            fused_pool = (li + 1 < len(VGG16_CONVS)
-                                          and VGG16_CONVS[li + 1][0] == 'pool')
-                            x = ops.conv3x3_nhwc_f16x2(x, wp, b, True, out=dst, amax_in=bound,
-                                                       in_mul=mul, in_add=add, amax_out=word,
-                                                       pool2=fused_pool, amax_out_zeroed=zeroed,
-                                                       dilation=d)
-                        else:                            # Winograd, f16 batch GEMMs
-                            x = ops.conv3x3_winograd_nhwc_f16x2(x, wp, b, d, True, out=dst,
-                                                                amax_in=bound, amax_out=word)
-                        prev = li
-                    elif self.mfma_dtype == 'bf16' and wp.dtype == torch.bfloat16:
-                        fused_pool = (d == 1 and dst is None and li + 1 < len(VGG16_CONVS)
-                                      and VGG16_CONVS[li + 1][0] == 'pool')
-                        x = ops.conv3x3_nhwc_bf16_wp(x, wp, b, d, True, out=dst, pool2=fused_pool)
-                        prev = None
-                    else:
-                        if wp.dtype == torch.bfloat16:
-                            conv = (ops.conv3x3_winograd_nhwc_f32x3 if self.conv_wino[name]
-                                    else ops.conv3x3_nhwc_f32x3)
-                        elif self.mfma_dtype == 'bf16':
-                            conv = ops.conv3x3_nhwc_bf16
-                        else:
-                            conv = (ops.conv3x3_winograd_nhwc if self.conv_wino[name]
-                                    else ops.conv3x3_nhwc)
-                        if (conv is ops.conv3x3_nhwc_f32x3 and d == 1 and dst is None
-                                and li + 1 < len(VGG16_CONVS) and VGG16_CONVS[li + 1][0] == 'pool'
-                                and wp.shape[-2] % 64 == 0 and wp.shape[-2] <= 256):
-                            x = conv(x, wp, b, d, True, pool2=True)     # pool1..3 in the epilogue
-                            fused_pool = True
-                        else:
-                            x = conv(x, wp, b, d, True, out=dst)
-                        prev = None
-        self._pool_done = fused_pool     # a range that ends on a fused pool: the next one skips it
-        return x
+            form, w, b, d = s.form, lay.operand, lay.b, s.dilation
+            if lay.direct is not None:
+                # direct 2 x f16 halo-tile kernel where it fills the chip (>= one 8x32-pixel x
+                # 128-channel tile per CU: conv3_x at 600x1000, and every deep layer once the
+                # images share a launch), Winograd below that
+                tiles = x.shape[0] * ((x.shape[1] + 7) // 8) * ((x.shape[2] + 31) // 32)
+                if tiles * (s.cout // 128) >= self.DIRECT_MIN_TILES:
+                    form, w = 'h2_direct', lay.direct
+            if aff != _IDENTITY and form != 'h2_direct':
+                raise ValueError('%s: its input bound carries (mul, add) = %r, which the %s form '
+                                 'cannot apply' % (s.name, aff, form))
+            last = k == len(layers) - 1
+            dst = out if last else None
+            pooled = s.pool2 and form in ('h2_direct', 'x3_direct', 'bf16_wp')
+            word, word_aff = None, _IDENTITY          # the bound this layer hands on
+            if form in _H2_FORMS:
+                word = amax_out if last and amax_out is not None else words[k:k + 1]
+            if form == 'c3':
+                y = ops.conv3x3_c3_nchw_to_nhwc(x, w, b, True)
+                if lay.affine is not None:
+                    word, word_aff = ops.amax_word(x), lay.affine     # 7 MB: the network input
+                x = y
+            elif form == 'h2_direct':
+                x = ops.conv3x3_nhwc_f16x2(x, w, b, True, out=dst, amax_in=bound, in_mul=aff[0],
+                                           in_add=aff[1], amax_out=word, pool2=pooled,
+                                           amax_out_zeroed=word is not amax_out, dilation=d)
+            elif form in ('h2_wino2', 'h2_wino4'):
+                x = ops.conv3x3_winograd_nhwc_f16x2(x, w, b, d, True, out=dst, amax_in=bound,
+                                                    amax_out=word)
+            elif form == 'x3_direct':
+                x = ops.conv3x3_nhwc_f32x3(x, w, b, d, True, out=dst, pool2=pooled)
+            elif form == 'x3_wino':
+                x = ops.conv3x3_winograd_nhwc_f32x3(x, w, b, d, True, out=dst)
+            elif form == 'f32_direct':
+                x = ops.conv3x3_nhwc(x, w, b, d, True, out=dst)
+            elif form == 'f32_wino':
+                x = ops.conv3x3_winograd_nhwc(x, w, b, d, True, out=dst)
+            elif form == 'bf16_wp':
+                x = ops.conv3x3_nhwc_bf16_wp(x, w, b, d, True, out=dst, pool2=pooled)
+            bound, aff = word, word_aff
+        return ChainState(x, bound, aff, pooled)
 
     def conv_body(self, data, roi_job=None):
         """data NCHW [B,3,H,W] -> conv5_3 NHWC [B,H/8-1,W/8-1,512].
@@ -615,32 +630,26 @@ class WsddnEngine(object):
         hardware packs the tail of one image's layer with the head of the other's."""
         n = data.shape[0]
         # fp16x2: max|conv5_3| per image (per chain) for the RoIPool -> fc6 operand scale
-        planes = (self.mfma_dtype == 'fp16x2' and self.k6 % 32 == 0
-                  and isinstance(self.conv[VGG16_CONVS[-1][0]][0], ops.F16x2))
+        planes = self.conv_layers[-1].step.form in _H2_FORMS
         per_image = n > 1 and self.conv_streams
-        self._pool_done = False
         self._roi_maps = None
         self._roi_operand = None
         self._amax5 = (torch.empty((n if per_image else 1,), device=self.device,
                                    dtype=torch.int32) if planes else None)
-        heads_first = self.mfma_dtype in ('fp16x2', 'bf16')
-        if self._update_waiting and (not per_image or not heads_first):
+        if self._update_waiting and (not per_image or not self._update_behind_heads):
             self._launch_update(())        # no per-image conv1_1 head to put it behind
         if not per_image:
-            res = self._conv_chain(data, amax_final=self._amax5)
+            res = self._conv_chain(self.conv_layers, ChainState(data, None, _IDENTITY, False),
+                                   amax_out=self._amax5).x
             self._roi_maps_of = (res.data_ptr(), res._version)
             return res
         h, w = data.shape[2], data.shape[3]
-        for _ in range(3):
-            h, w = (h - 2) // 2 + 1, (w - 2) // 2 + 1
-        if self.dilation == 2:
-            h, w = h - 1, w - 1
-        else:
-            h, w = (h - 2) // 2 + 1, (w - 2) // 2 + 1
+        for s in (lay.step for lay in self.conv_layers if lay.step.form == 'pool'):
+            h, w = (h - 2) // s.stride + 1, (w - 2) // s.stride + 1
         out = torch.empty((n, h, w, 512), device=self.device, dtype=torch.float32)
         # (bf16 plan: RoIPoolF writes fc6's one-plane operand over the same maps)
-        slab = self.mfma_dtype == 'bf16' and self.k6 % 64 == 0
-        self._roi_maps = (torch.empty_like(out), torch.empty_like(out)) if (planes or slab) else None
+        self._roi_maps = ((torch.empty_like(out), torch.empty_like(out))
+                          if self._roi_maps_on_chains else None)
         # the maps belong to THIS tensor in THIS state (_take_roi_maps)
         self._roi_maps_of = (out.data_ptr(), out._version)
         pooled = None
@@ -652,47 +661,31 @@ class WsddnEngine(object):
         start = main.record_event()
         while len(self._streams) < n:
             self._streams.append(side_stream(self.device, 'conv%d' % len(self._streams)))
-        split = (self._update_waiting and heads_first)
-        h2 = self.mfma_dtype == 'fp16x2'     # operand-scale bounds travel along the chain
+        chains = [ChainState(data[i:i + 1], None, _IDENTITY, False) for i in range(n)]
+        layers = self.conv_layers
+        split = self._update_waiting and self._update_behind_heads
         if split:
             # the head of every image's chain first (conv1_1: HBM-bound, 0.06 ms alone), THEN the
             # deferred parameter update, then the rest of the chains: started together, the SGD
             # kernel's workgroups fill the CUs and the two conv1_1 launches at the head of the
             # dependent chains took 0.7 ms each (kernel trace)
-            heads, evs = [], []
+            ua = min(max(1, self.UPDATE_AFTER), len(layers) - 1)
+            evs = []
             for i in range(n):
                 st = self._streams[i]
                 st.wait_event(start)
                 with torch.cuda.stream(st):
-                    if self.UPDATE_AFTER <= 1:
-                        wp, b, _w = self.conv['conv1_1']
-                        y = ops.conv3x3_c3_nchw_to_nhwc(data[i:i + 1], wp, b, True)
-                        bound, aff = ((ops.amax_word(data[i:i + 1]), self._c11_bound) if h2
-                                      else (None, None))
-                    else:
-                        # ... and conv1_2 (+ pool1): the other HBM-heavy layer of the chain
-                        bound = (torch.zeros((1,), device=self.device, dtype=torch.int32) if h2
-                                 else None)
-                        y = self._conv_chain(data[i:i + 1], first=0, end=self.UPDATE_AFTER,
-                                             amax_last=bound)
-                        aff = None
-                    heads.append((y, bound, aff))
+                    chains[i] = self._conv_chain(layers[:ua], chains[i])
                     evs.append(st.record_event())
-            pool_done = self._pool_done
             self._launch_update(evs)
+            layers = layers[ua:]
         for i in range(n):
             st = self._streams[i]
             if not split:
                 st.wait_event(start)
             with torch.cuda.stream(st):
                 af = None if self._amax5 is None else self._amax5[i:i + 1]
-                if split:
-                    self._pool_done = pool_done
-                    self._conv_chain(None, out=out[i:i + 1], amax_final=af,
-                                     first=max(1, self.UPDATE_AFTER), x=heads[i][0],
-                                     bound_in=heads[i][1], affine_in=heads[i][2])
-                else:
-                    self._conv_chain(data[i:i + 1], out=out[i:i + 1], amax_final=af)
+                self._conv_chain(layers, chains[i], out=out[i:i + 1], amax_out=af)
                 if self._roi_maps is not None:
                     # RoIPoolF's block-maxima maps of this image, beside the other image's tail
                     ops.roi_maxmaps(out[i:i + 1], self._roi_maps[0][i:i + 1], self._roi_maps[1][i:i + 1])

@@ -272,6 +272,49 @@ def test_engine_host_scheduling_helpers():
     assert op.inv_scale.data_ptr() == op.scales[1].data_ptr()
 
 
+def test_engine_conv_plan_forms():
+    """engine.conv_plan, the one place that chooses how each conv layer runs: the forms of the four
+    arithmetic plans under dilation 1 / 2 and WINO_F4_MIN_CIN 256 (default) / 512 / 0."""
+    from naws_hip.engine import VGG16_CONVS, conv_plan
+
+    def entry(s):
+        if s.form == 'pool':
+            return 'pool%d' % s.stride
+        return s.form + '/direct' * s.direct_alt + '+pool' * s.pool2 + '+bound' * s.weight_bound
+
+    # dilation 2; entries 0-16 = conv1_1 conv1_2 pool1 conv2_1 conv2_2 pool2 conv3_1 conv3_2 conv3_3
+    # pool3 conv4_1 conv4_2 conv4_3 pool4 conv5_1 conv5_2 conv5_3
+    h2_head = ('c3+bound h2_direct+pool pool2 h2_direct h2_direct+pool pool2 '
+               'h2_wino2/direct h2_wino2/direct h2_wino2/direct+pool pool2 ')
+    table = {
+        ('fp16x2', 256): h2_head + 'h2_wino4 h2_wino4 h2_wino4 pool1 h2_wino4 h2_wino4 h2_wino4',
+        ('fp16x2', 512): h2_head + 'h2_wino2/direct h2_wino4 h2_wino4 pool1 h2_wino4 h2_wino4 '
+                                   'h2_wino4',
+        ('fp16x2', 0): h2_head + 'h2_wino2/direct h2_wino2/direct h2_wino2/direct pool1 '
+                                 'h2_wino2/direct h2_wino2/direct h2_wino2/direct',
+        'fp32x3': 'c3 x3_direct+pool pool2 x3_direct x3_direct+pool pool2 x3_direct x3_direct '
+                  'x3_direct+pool pool2 x3_wino x3_wino x3_wino pool1 x3_wino x3_wino x3_wino',
+        'fp32': 'c3 f32_direct pool2 f32_direct f32_direct pool2 f32_wino f32_wino f32_wino pool2 '
+                'f32_wino f32_wino f32_wino pool1 f32_wino f32_wino f32_wino',
+        'bf16': 'c3 bf16_wp+pool pool2 bf16_wp bf16_wp+pool pool2 bf16_wp bf16_wp bf16_wp+pool '
+                'pool2 bf16_wp bf16_wp bf16_wp pool1 bf16_wp bf16_wp bf16_wp',
+    }
+    layers = [item[:3] for item in VGG16_CONVS if not item[0].startswith('pool')]
+    for plan in ('fp16x2', 'fp32x3', 'fp32', 'bf16'):
+        for dilation in (1, 2):
+            for f4 in (256, 512, 0):
+                want = table[(plan, f4) if plan == 'fp16x2' else plan].split()
+                if dilation == 1:
+                    want[13] = 'pool2'              # pool4: stride 2, conv5_x undilated
+                got = conv_plan(plan, dilation, f4)
+                assert [entry(s) for s in got] == want, (plan, dilation, f4)
+                convs = [s for s in got if s.form != 'pool']
+                assert [(s.name, s.cin, s.cout) for s in convs] == layers
+                assert [s.dilation for s in convs] == [1] * 10 + [dilation] * 3
+    with pytest.raises(ValueError):
+        conv_plan('fp16', 2, 256)
+
+
 def test_checkpoint_preserved_blobs_round_trip(tmp_path, cfgmod):
     """Blobs of the weights file that the model does not use are carried through load -> save
     under their UNSCOPED names (reference net_wsl.py:129-137 keeps them as '__preserve__/<name>'

@@ -569,27 +569,37 @@ def test_per_image_pooling_on_the_conv_streams_is_bit_identical(dev):
     assert torch.isfinite(res[0][2]).all()
 
 
-def test_default_plan_runs_winograd4_on_the_512_channel_layers_and_f2_agrees(dev):
+def test_default_plan_conv_layers_carry_winograd4_on_the_512_channel_layers_and_f2_agrees(dev):
     """The default plan's conv forms (engine.set_conv_blobs): conv4_1 .. conv5_3 carry the 36-frequency
     planes of Winograd F(4x4,3x3) (csrc/winograd4.hip), conv3_x the F(2x2) planes + the direct kernel's
     (chosen per input size), conv1_2 .. conv2_2 the direct kernel's; WINO_F4_MIN_CIN = 0 brings the
-    F(2x2) plan of rounds 1-5 back, and the two conv bodies agree to 1e-5 of max|conv5_3|."""
+    F(2x2) plan of rounds 1-5 back, and the two conv bodies agree to 1e-5 of max|conv5_3|.  A conv
+    weight of the wrong shape is refused."""
     from naws_hip import ops
     from naws_hip.engine import WsddnEngine
+
+    def layers(e):
+        return {lay.step.name: lay for lay in e.conv_layers if lay.w is not None}
+
     eng, mb, blobs = _setup(dev, mfma_dtype='fp16x2')
+    convs = layers(eng)
     for name in ('conv4_1', 'conv4_2', 'conv4_3', 'conv5_1', 'conv5_2', 'conv5_3'):
-        wp = eng.conv[name][0]
+        wp = convs[name].operand
         assert isinstance(wp, ops.F16x2) and wp.planes.dim() == 5 and wp.planes.shape[1] == 36, name
-        assert name not in eng.conv_direct_h2
+        assert convs[name].direct is None
     for name in ('conv3_2', 'conv3_3'):
-        assert eng.conv[name][0].planes.shape[1] == 16 and name in eng.conv_direct_h2
+        assert convs[name].operand.planes.shape[1] == 16 and convs[name].direct is not None
     for name in ('conv1_2', 'conv2_1', 'conv2_2'):
-        assert eng.conv[name][0].planes.dim() == 4
+        assert convs[name].operand.planes.dim() == 4
     data = torch.from_numpy(mb['data']).to(dev)
     y4 = eng.conv_body(data).clone()
     eng2 = WsddnEngine(21, dev, dropout=0.5, gpu_num=2, seed=11, mfma_dtype='fp16x2')
     eng2.WINO_F4_MIN_CIN = 0
     eng2.set_conv_blobs(blobs)
-    assert eng2.conv['conv4_2'][0].planes.shape[1] == 16
+    assert layers(eng2)['conv4_2'].operand.planes.shape[1] == 16
     y2 = eng2.conv_body(data)
     assert float((y4 - y2).abs().max()) <= 1e-5 * float(y2.abs().max())
+    bad = dict(blobs, conv3_2_w=blobs['conv3_2_w'][:, :128])
+    with pytest.raises(ValueError, match='conv3_2_w'):
+        eng2.set_conv_blobs(bad)
+    assert layers(eng2)['conv3_2'].w.shape == (256, 256, 3, 3)

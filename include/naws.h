@@ -107,6 +107,36 @@ int naws_roi_pool_f_fwd(const float* X, int layout, int N, int C, int H, int W,
                         int pooled_h, int pooled_w, float spatial_scale,
                         float* Y, int32_t* argmax, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * RoIContext / RoILoopPool: the contextual WSDDN head (WSL.CONTEXT)
+ *   ref: detectron/modeling/wsl_heads.py:684-766 (op emission),
+ *        detectron/ops/roi_context_op.cu, detectron/ops/roi_loop_pool_op.cu.
+ *
+ * naws_roi_context_fwd: rois [R,5] -> frame [R,9] and context [R,9]; columns
+ * 0..4 are (batch_idx, outer rectangle), 5..8 the inner rectangle.  With
+ * w = x2-x1, ri = w - w/ratio, ro = w*ratio - w (likewise for h; fp32, every
+ * operation rounded on its own - no FMA):
+ *   frame   = (b, x1, y1, x2, y2, x1+ri_w/2, y1+ri_h/2, x2-ri_w/2, y2-ri_h/2)
+ *   context = (b, x1-ro_w/2, y1-ro_h/2, x2+ro_w/2, y2+ro_h/2, x1, y1, x2, y2)
+ * The frame's inner and the context's outer rectangle are clamped to
+ * [0,max_w] x [0,max_h] (the dims of the padded image blob, not max-1).
+ * Errors: R<0 -> SHAPE; context_ratio<=0 -> ARG.
+ *
+ * naws_roi_loop_pool_fwd: naws_roi_pool_f_fwd on columns 1..4 of rois9 [R,9]
+ * (same layouts, boost, argmax and errors) with two differences: a pixel
+ * (h,w) with sh<h<eh and sw<w<ew is skipped, the inner edges being
+ * roundf(column 5..8 * spatial_scale) (strict: the hole's border is pooled);
+ * and the running maximum of EVERY bin starts at 0 with a strict '>', so a
+ * bin with nothing positive outside the hole is (0, argmax -1).
+ * pooled_w > 64 or pooled_h*pooled_w beyond the LDS staging -> UNSUPPORTED.
+ * ------------------------------------------------------------------------ */
+int naws_roi_context_fwd(const float* rois, int R, float context_ratio, int max_h, int max_w,
+                         float* frame, float* context, void* stream);
+int naws_roi_loop_pool_fwd(const float* X, int layout, int N, int C, int H, int W,
+                           const float* rois9, int R, const float* boost,
+                           int pooled_h, int pooled_w, float spatial_scale,
+                           float* Y, int32_t* argmax, void* stream);
+
 /* Y[r,f] = X[r,f] * S[r]   (in place allowed)  ref: roi_feature_boost_op.cc:8-35 */
 int naws_roi_feature_boost_fwd(const float* X, const float* S, int R, int F, float* Y,
                                void* stream);

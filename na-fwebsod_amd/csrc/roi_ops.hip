@@ -1,4 +1,5 @@
-// RoIPoolF (+ fused RoIFeatureBoost), RoIFeatureBoost fwd/bwd, RoIIoU for gfx950.
+// RoIPoolF (+ fused RoIFeatureBoost), RoIFeatureBoost fwd/bwd, RoIIoU, RoIContext and
+// RoILoopPool (the contextual head, at the end of the file) for gfx950.
 //
 // ref: detectron/ops/roi_loop_pool_op.cu:31-101 (RoIPoolF arithmetic; :72 original
 //      empty-bin rule), detectron/ops/roi_feature_boost_op.cc:8-66,
@@ -856,5 +857,256 @@ extern "C" int naws_roi_iou_fwd(const float* rois, int R, float* J, void* stream
   NAWS_REQUIRE_PTR(J);
   dim3 grid((unsigned)naws_cdiv(R, 256), R);
   hipLaunchKernelGGL(roi_iou_kernel, grid, dim3(256), 0, (hipStream_t)stream, rois, R, J);
+  return naws_check_launch();
+}
+
+// ---- RoIContext / RoILoopPool: the contextual WSDDN head (WSL.CONTEXT) ------------------------
+// ref: detectron/ops/roi_context_op.cu, detectron/ops/roi_loop_pool_op.cu (arithmetic only).
+namespace {
+
+// rois [R,5] -> frame [R,9] / context [R,9]: columns 0..4 the outer rectangle, 5..8 the inner one.
+// Bit-exact against a float32 restatement, so every operation is rounded on its own: no FMA may
+// be formed from w * ratio - w (the library is built with -ffp-contract=fast-honor-pragmas).
+__global__ __launch_bounds__(256) void roi_context_kernel(const float* __restrict__ rois, int R,
+                                                          float ratio, float max_h, float max_w,
+                                                          float* __restrict__ frame,
+                                                          float* __restrict__ context) {
+#pragma clang fp contract(off)
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  const float b = rois[r * 5 + 0];
+  const float x1 = rois[r * 5 + 1], y1 = rois[r * 5 + 2];
+  const float x2 = rois[r * 5 + 3], y2 = rois[r * 5 + 4];
+  const float w = x2 - x1, h = y2 - y1;
+  const float iw = w / ratio, ih = h / ratio;
+  const float ow = w * ratio, oh = h * ratio;
+  const float ri_w = w - iw, ri_h = h - ih;
+  const float ro_w = ow - w, ro_h = oh - h;
+  const float hi_w = ri_w / 2.0f, hi_h = ri_h / 2.0f;
+  const float ho_w = ro_w / 2.0f, ho_h = ro_h / 2.0f;
+  auto clamp = [](float v, float m) { return v < 0.0f ? 0.0f : (v > m ? m : v); };
+  float* f = frame + (int64_t)r * 9;
+  f[0] = b; f[1] = x1; f[2] = y1; f[3] = x2; f[4] = y2;
+  f[5] = clamp(x1 + hi_w, max_w);
+  f[6] = clamp(y1 + hi_h, max_h);
+  f[7] = clamp(x2 - hi_w, max_w);
+  f[8] = clamp(y2 - hi_h, max_h);
+  float* c = context + (int64_t)r * 9;
+  c[0] = b;
+  c[1] = clamp(x1 - ho_w, max_w);
+  c[2] = clamp(y1 - ho_h, max_h);
+  c[3] = clamp(x2 + ho_w, max_w);
+  c[4] = clamp(y2 + ho_h, max_h);
+  c[5] = x1; c[6] = y1; c[7] = x2; c[8] = y2;
+}
+
+// RoILoopPool: RoIPoolF's bin geometry on columns 1..4 of a 9-column roi, minus the pixels
+// strictly inside the inner rectangle (columns 5..8), with the running maximum starting at 0
+// (strict '>'): a bin with nothing positive outside the hole is (0, argmax -1).
+//
+// One workgroup (4 waves) = one roi x 64 channels, for either layout.  The bin maxima are staged in
+// LDS as [64 channels][PH*PW] with an odd channel stride (bank-conflict free when 64 lanes write
+// the same bin of 64 channels) and leave as ONE contiguous run of 64*PH*PW floats of Y (the
+// 49-float rows of 64 consecutive channels are adjacent).  Only the gather differs:
+//   NHWC  lane = channel: every window pixel is one 256-byte read per wave; the bins are dealt
+//         round-robin to the waves.  The hole cuts a window row into at most two runs, so the
+//         inner loops carry no predicate.
+//   NCHW  wave = channel, lane = column of the roi: a row of the bin row's span is one contiguous
+//         read per wave.  Every lane keeps its column's maximum, the columns meet in a per-wave LDS
+//         strip and lane pw folds the columns of bin pw.
+// Maxima combine as (greater value, or equal value and smaller index) from (0, -1): the result of
+// the sequential h-major scan with a strict '>' whatever the order of combination.
+constexpr int LP_CH = 64;      // channels per workgroup
+constexpr int LP_WAVES = 4;
+
+struct LoopRoi {
+  RoiBins rb;
+  int sw_in, sh_in, ew_in, eh_in;   // the hole: pixels strictly inside are skipped
+  bool valid;                       // batch index inside [0, N)
+};
+
+__device__ __forceinline__ LoopRoi loop_roi(const float* roi, float spatial_scale, int N) {
+  LoopRoi lr;
+  lr.rb = roi_frame(roi, spatial_scale);
+  lr.sw_in = (int)roundf(roi[5] * spatial_scale);
+  lr.sh_in = (int)roundf(roi[6] * spatial_scale);
+  lr.ew_in = (int)roundf(roi[7] * spatial_scale);
+  lr.eh_in = (int)roundf(roi[8] * spatial_scale);
+  lr.valid = lr.rb.batch >= 0 && lr.rb.batch < N;
+  return lr;
+}
+
+#define NAWS_LP_UPD(v, i) if ((v) > best) { best = (v); besti = (i); }
+
+template <bool NHWC, bool WITH_ARGMAX>
+__global__ __launch_bounds__(64 * LP_WAVES) void roi_loop_pool_kernel(
+    const float* __restrict__ X, int N, int C, int H, int W, const float* __restrict__ rois9,
+    const float* __restrict__ boost, int PH, int PW, float spatial_scale, int nslices,
+    float* __restrict__ Y, int32_t* __restrict__ argmax) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int nb = PH * PW;
+  const int stride = nb | 1;                                     // odd: see above
+  float* tile = reinterpret_cast<float*>(smem_raw);               // [LP_CH][stride]
+  int32_t* itile = reinterpret_cast<int32_t*>(tile + LP_CH * stride);   // (WITH_ARGMAX)
+  const int slice = blockIdx.x % nslices;
+  const int r = blockIdx.x / nslices;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int c0 = slice * LP_CH;
+  const int nch = min(LP_CH, C - c0);
+
+  const LoopRoi lr = loop_roi(rois9 + (int64_t)r * 9, spatial_scale, N);
+  const RoiBins rb = lr.rb;
+  const float bin_h = (float)rb.roi_h / (float)PH;
+  const float bin_w = (float)rb.roi_w / (float)PW;
+  const float scale = boost ? boost[r] : 1.0f;
+
+  if constexpr (NHWC) {
+    const bool active = lr.valid && lane < nch;
+    const float* Xn = X + (int64_t)(lr.valid ? rb.batch : 0) * H * W * C + c0 + (active ? lane : 0);
+    for (int bin = wave; bin < nb; bin += LP_WAVES) {
+      const int ph = bin / PW, pw = bin - ph * PW;
+      int hs, he, ws, we;
+      bin_range(ph, bin_h, rb.start_h, H, hs, he);
+      bin_range(pw, bin_w, rb.start_w, W, ws, we);
+      float best = 0.0f;
+      int besti = -1;
+      if (active) {
+        for (int h = hs; h < he; ++h) {
+          // runs [ws, a1) and [b0, we): the row minus the open interval (sw_in, ew_in)
+          int a1 = we, b0 = we;
+          if (h > lr.sh_in && h < lr.eh_in) {
+            a1 = min(max(lr.sw_in + 1, ws), we);
+            b0 = min(max(lr.ew_in, a1), we);
+          }
+          const float* row = Xn + (int64_t)h * W * C;
+          const int base = h * W;
+          int w = ws;
+          for (int run = 0; run < 2; ++run) {
+            const int end = run == 0 ? a1 : we;
+            for (; w + 4 <= end; w += 4) {                        // 4 independent loads in flight
+              const float v0 = row[(int64_t)(w + 0) * C];
+              const float v1 = row[(int64_t)(w + 1) * C];
+              const float v2 = row[(int64_t)(w + 2) * C];
+              const float v3 = row[(int64_t)(w + 3) * C];
+              NAWS_LP_UPD(v0, base + w) NAWS_LP_UPD(v1, base + w + 1)
+              NAWS_LP_UPD(v2, base + w + 2) NAWS_LP_UPD(v3, base + w + 3)
+            }
+            for (; w < end; ++w) {
+              const float v = row[(int64_t)w * C];
+              NAWS_LP_UPD(v, base + w)
+            }
+            w = b0;
+          }
+        }
+      }
+      tile[lane * stride + bin] = best * scale;
+      if (WITH_ARGMAX) itile[lane * stride + bin] = besti;
+    }
+  } else {
+    __shared__ float2 strip[LP_WAVES][64];                        // (column maximum, index bits)
+    // the columns the bins cover: bins abut or overlap, so their union is one span
+    int x0, x1, t0, t1;
+    bin_range(0, bin_w, rb.start_w, W, x0, t0);
+    bin_range(PW - 1, bin_w, rb.start_w, W, t1, x1);
+    int bws = 0, bwe = 0;                                         // lane pw: columns of bin pw
+    if (lane < PW) bin_range(lane, bin_w, rb.start_w, W, bws, bwe);
+    for (int ch = wave; ch < nch; ch += LP_WAVES) {
+      const float* Xc = X + ((int64_t)(lr.valid ? rb.batch : 0) * C + c0 + ch) * H * W;
+      for (int ph = 0; ph < PH; ++ph) {
+        int hs, he;
+        bin_range(ph, bin_h, rb.start_h, H, hs, he);
+        float best = 0.0f;                                        // lanes < PW: the bin's maximum
+        int besti = -1;
+        for (int wb = x0; wb < x1 && lr.valid; wb += 64) {
+          const int w = wb + lane;
+          float cv = 0.0f;
+          int ci = -1;
+          if (w < x1) {
+            const bool in_cols = w > lr.sw_in && w < lr.ew_in;
+            for (int h = hs; h < he; ++h) {
+              if (in_cols && h > lr.sh_in && h < lr.eh_in) continue;
+              const float v = Xc[h * W + w];
+              if (v > cv) { cv = v; ci = h * W + w; }
+            }
+          }
+          __builtin_amdgcn_wave_barrier();                        // (the strip's previous readers)
+          strip[wave][lane] = make_float2(cv, __int_as_float(ci));
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          if (lane < PW) {
+            const int lo = max(bws, wb), hi = min(bwe, min(wb + 64, x1));
+            for (int j = lo; j < hi; ++j) {
+              const float2 e = strip[wave][j - wb];
+              const int ei = __float_as_int(e.y);
+              if (e.x > best || (e.x == best && ei >= 0 && ei < besti)) { best = e.x; besti = ei; }
+            }
+          }
+        }
+        if (lane < PW) {
+          tile[ch * stride + ph * PW + lane] = best * scale;
+          if (WITH_ARGMAX) itile[ch * stride + ph * PW + lane] = besti;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // Y[r][c0 .. c0+nch)[:] is one contiguous run of nch * nb floats
+  const int count = nch * nb;
+  const int64_t obase = ((int64_t)r * C + c0) * nb;
+  for (int i = threadIdx.x; i < count; i += 64 * LP_WAVES) {
+    const int cl = i / nb, k = i - cl * nb;
+    Y[obase + i] = tile[cl * stride + k];
+    if (WITH_ARGMAX) argmax[obase + i] = itile[cl * stride + k];
+  }
+}
+#undef NAWS_LP_UPD
+
+}  // namespace
+
+extern "C" int naws_roi_context_fwd(const float* rois, int R, float context_ratio, int max_h,
+                                    int max_w, float* frame, float* context, void* stream) {
+  if (R < 0) return NAWS_ERR_SHAPE;
+  if (!(context_ratio > 0.0f)) return NAWS_ERR_ARG;
+  if (R == 0) return NAWS_OK;
+  NAWS_REQUIRE_PTR(rois);
+  NAWS_REQUIRE_PTR(frame);
+  NAWS_REQUIRE_PTR(context);
+  hipLaunchKernelGGL(roi_context_kernel, dim3((unsigned)naws_cdiv(R, 256)), dim3(256), 0,
+                     (hipStream_t)stream, rois, R, context_ratio, (float)max_h, (float)max_w, frame,
+                     context);
+  return naws_check_launch();
+}
+
+extern "C" int naws_roi_loop_pool_fwd(const float* X, int layout, int N, int C, int H, int W,
+                                      const float* rois9, int R, const float* boost, int pooled_h,
+                                      int pooled_w, float spatial_scale, float* Y, int32_t* argmax,
+                                      void* stream) {
+  if (R < 0 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || pooled_h <= 0 || pooled_w <= 0)
+    return NAWS_ERR_SHAPE;
+  if (layout != NAWS_LAYOUT_NCHW && layout != NAWS_LAYOUT_NHWC) return NAWS_ERR_ARG;
+  if (R == 0) return NAWS_OK;
+  NAWS_REQUIRE_PTR(X);
+  NAWS_REQUIRE_PTR(rois9);
+  NAWS_REQUIRE_PTR(Y);
+  const int64_t nb = (int64_t)pooled_h * pooled_w;
+  const int nslices = (int)naws_cdiv(C, LP_CH);
+  const int64_t lds = (int64_t)LP_CH * (nb | 1) * sizeof(float) * (argmax ? 2 : 1);
+  // (the NCHW gather folds bin pw on lane pw; h * W + w is an int32 argmax)
+  if (lds > 60 * 1024 || pooled_w > 64 || (int64_t)H * W > 0x7fffffffLL ||
+      (int64_t)R * nslices > 0x7fffffffLL)
+    return NAWS_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)((int64_t)R * nslices)), block(64 * LP_WAVES);
+#define NAWS_LP_LAUNCH(L, A)                                                                      \
+  hipLaunchKernelGGL((roi_loop_pool_kernel<L, A>), grid, block, (size_t)lds, s, X, N, C, H, W,    \
+                     rois9, boost, pooled_h, pooled_w, spatial_scale, nslices, Y, argmax)
+  if (layout == NAWS_LAYOUT_NHWC) {
+    if (argmax) NAWS_LP_LAUNCH(true, true); else NAWS_LP_LAUNCH(true, false);
+  } else {
+    if (argmax) NAWS_LP_LAUNCH(false, true); else NAWS_LP_LAUNCH(false, false);
+  }
+#undef NAWS_LP_LAUNCH
   return naws_check_launch();
 }

@@ -227,6 +227,12 @@ class NetExecutor(object):
         elif t == 'RoIPoolF':
             ws[out[0]], ws[out[1]] = O.RoIPoolF(x[0], x[1], a['pooled_h'], a['pooled_w'],
                                                 a['spatial_scale'])
+        elif t == 'RoIContext':      # inputs (rois, data): the clamp bounds are the image blob's dims
+            ws[out[0]], ws[out[1]] = O.RoIContext(x[0], ws['data'],
+                                                  context_ratio=a.get('context_ratio', 1.8))
+        elif t == 'RoILoopPool':
+            ws[out[0]], ws[out[1]] = O.RoILoopPool(x[0], x[1], a['pooled_h'], a['pooled_w'],
+                                                   a['spatial_scale'])
         elif t == 'RoIFeatureBoost':
             ws[out[0]] = O.RoIFeatureBoost(x[0], x[1])
         elif t == 'FC':
@@ -323,7 +329,8 @@ class NetExecutor(object):
         gout = [ws[g] if g else None for g in a['_gout']]
         res = [None] * n_in
         if t == 'FC':
-            dW, db, dX = O.FCGradient(ws[ins[0]], ws[ins[1]], gout[0].contiguous())
+            dW, db, dX = O.FCGradient(ws[ins[0]], ws[ins[1]], gout[0].contiguous(),
+                                      need_dx=a['_gin'][0] is not None)
             res = [dX, dW, db]
         elif t == 'Relu':
             res = [O.ReluGradient(ws[outs[0]], gout[0])]
@@ -338,6 +345,8 @@ class NetExecutor(object):
             res = [O.Mul(gout[0], ws[ins[1]]), O.Mul(gout[0], ws[ins[0]])]
         elif t == 'Add':
             res = [gout[0], gout[0]]
+        elif t == 'Sub':
+            res = [gout[0], O.Scale(gout[0], scale=-1.0)]
         elif t == 'ReduceSum':      # broadcast the [1,C] gradient down the rows
             res = [O.Mul(O.ConstantFill(like=ws[ins[0]], value=1.0), gout[0])]
         elif t == 'AveragedLoss':

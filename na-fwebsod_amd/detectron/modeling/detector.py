@@ -48,12 +48,12 @@ class Net(object):
 # op type -> indices of the inputs that receive a gradient (others are treated as constants)
 _GRAD_INPUTS = {
     'FC': (0, 1, 2), 'Relu': (0,), 'Dropout': (0,), 'Softmax': (0,), 'Transpose': (0,),
-    'Mul': (0, 1), 'Add': (0, 1), 'ReduceSum': (0,), 'AveragedLoss': (0,),
+    'Mul': (0, 1), 'Add': (0, 1), 'Sub': (0, 1), 'ReduceSum': (0,), 'AveragedLoss': (0,),
     'WeightedCrossEntropyWithLogits': (0,), 'CrossEntropyWithLogits': (0,),
     'RoIFeatureBoost': (0,), 'MinEntropyLoss': (0,), 'SoftmaxWithLossN': (0,),
 }
 _NO_GRAD = {'StopGradient', 'RoIIoU', 'Stat', 'Accuracy', 'ConstantFill', 'Shape', 'Cast',
-            'DequeueBlobs', 'RoILabel', 'RoIEntropy', 'BoxWithNMSLimit'}
+            'DequeueBlobs', 'RoILabel', 'RoIEntropy', 'BoxWithNMSLimit', 'RoIContext'}
 
 
 class DetectionModelHelper(object):
@@ -141,7 +141,7 @@ class DetectionModelHelper(object):
     def RoIFeatureTransform(self, blobs_in, blob_out, blob_rois='rois', method='RoIPoolF',
                             resolution=7, spatial_scale=1. / 16., sampling_ratio=0):
         """Single feature level only (FPN is outside the hot path).  ref: detector.py:268-331."""
-        assert method in {'RoIPoolF'}, 'Unknown pooling method: {}'.format(method)
+        assert method in {'RoIPoolF', 'RoILoopPool'}, 'Unknown pooling method: {}'.format(method)
         assert not isinstance(blobs_in, list), 'FPN RoI transforms are not on the hot path'
         out = self.net.add(method, [blobs_in, blob_rois], [blob_out, '_argmax_' + blob_out],
                            dict(pooled_w=resolution, pooled_h=resolution,
@@ -166,13 +166,21 @@ class DetectionModelHelper(object):
     def AddGradientOperators(self, loss_gradients):
         """Reverse-mode op generation over the recorded forward ops.  `loss_gradients` maps a
         loss blob to the blob holding its gradient seed (blob.py:167-173).  Blobs consumed by
-        several ops accumulate (`<name>_grad` summed); StopGradient and the ops in _NO_GRAD cut
-        the flow, so nothing upstream of `roi_feat` / `conv5_3` or inside the entropy gate gets
-        a gradient op."""
+        several ops accumulate (`<name>_grad` summed), parameters shared by several FC ops
+        (the context head's fc6 / fc7 / fc8d_frame) included; StopGradient and the ops in
+        _NO_GRAD cut the flow, so nothing upstream of `roi_feat` / `conv5_3` or inside the
+        entropy gate gets a gradient op.  An FC whose input comes from such an
+        op (or from outside the net) emits no input gradient: nothing would read it."""
         grad_of = {str(k): str(v) for k, v in loss_gradients.items()}
         ops = []
-        params = set(self.params)
-        for op in reversed(self.net.ops):
+        producer = {}           # forward index of an op -> {input blob: type of its latest producer}
+        latest = {}
+        for idx, op in enumerate(self.net.ops):
+            producer[idx] = {n: latest.get(n) for n in op.inputs}
+            for o in op.outputs:
+                latest[o] = op.type
+        for idx in range(len(self.net.ops) - 1, -1, -1):
+            op = self.net.ops[idx]
             if op.type in _NO_GRAD:
                 for o in op.outputs:
                     grad_of.pop(o, None)
@@ -186,12 +194,14 @@ class DetectionModelHelper(object):
             gin = []
             for i, name in enumerate(op.inputs):
                 gin.append(name + '_grad' if i in _GRAD_INPUTS[op.type] else None)
+            if op.type == 'FC' and (producer[idx][op.inputs[0]] is None or
+                                    producer[idx][op.inputs[0]] in _NO_GRAD):
+                gin[0] = None       # dX = dY W behind StopGradient: a GEMM nobody consumes
             # in-place ops (Relu fc6->fc6): the output's gradient is consumed here
             for o in op.outputs:
                 if o in op.inputs:
                     grad_of.pop(o, None)
-            accumulate = [g is not None and op.inputs[i] in grad_of and op.inputs[i] not in params
-                          for i, g in enumerate(gin)]
+            accumulate = [g is not None and op.inputs[i] in grad_of for i, g in enumerate(gin)]
             ops.append(Op(op.type + 'Gradient', list(op.inputs) + list(op.outputs),
                           [g for g in gin if g], dict(op.args, _gout=gouts, _gin=gin,
                                                       _accumulate=accumulate)))

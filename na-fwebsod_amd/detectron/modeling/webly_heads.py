@@ -126,6 +126,14 @@ def add_spatial_entropy_weight(model, rois_pred, cls_prob, rois):
 
 def add_VGG16_roi_2fc_noise_head(model, blob_in, dim_in, spatial_scale, prefix=''):
     """Clean 2-fc head plus a second 2-fc stack ('_[noisy]_*' params) on the SAME roi_feat."""
+    if cfg.WSL.CONTEXT:
+        # The reference's branch (webly_heads.py:482-487) calls
+        # add_VGG16_roi_context_2fc_noise_head, which exists nowhere in the reference tree:
+        # WEBLY.WEBLY_ON with WSL.CONTEXT dies there too.
+        raise AttributeError("module 'detectron.modeling.webly_heads' has no attribute "
+                             "'add_VGG16_roi_context_2fc_noise_head' (nor does the reference: "
+                             "WSL.CONTEXT has no webly head upstream, webly_heads.py:482-487; "
+                             "use WEBLY.WEBLY_ON False with wsl_heads.add_VGG16_roi_2fc_head)")
     clean, dim_out = add_VGG16_roi_2fc_head(model, blob_in, dim_in, spatial_scale, prefix=prefix)
     roi_size = cfg.FAST_RCNN.ROI_XFORM_RESOLUTION
     tag = '_[' + prefix + 'noisy]_'

@@ -2,8 +2,10 @@
 add_wsl_outputs (:23-78), add_cls_pred (:213-227), add_cross_entropy_loss (:292-302),
 add_VGG16_roi_2fc_head (:654-681), DropoutIfTraining (:1259-1267); and, one cfg flag away
 (WSL.OICR): add_wsl_oicr_outputs (:134-156), add_wsl_losses (:375-458),
-add_oicr_losses (:512-560).  The PCL / CMIL / CSC / context / center-loss heads of that file are
-other WSOD methods (cfg switches that core/config.py rejects)."""
+add_oicr_losses (:512-560); (WSL.CONTEXT, the ContextLocNet contrastive head):
+add_wsl_context_outputs (:185-209), add_VGG16_roi_context_2fc_head (:684-766).  The PCL / CMIL /
+CSC / center-loss heads of that file are other WSOD methods (cfg switches that core/config.py
+rejects)."""
 from detectron.core.config import cfg
 from detectron.utils.c2 import const_fill, gauss_fill
 import detectron.utils.blob as blob_utils
@@ -12,10 +14,13 @@ import detectron.utils.blob as blob_utils
 def add_wsl_outputs(model, blob_in, dim, prefix=''):
     """fc8c / fc8d -> softmax over classes x softmax over proposals -> rois_pred."""
     n_fg = model.num_classes - 1
-    fc8c = model.FC(blob_in, prefix + 'fc8c', dim, n_fg, weight_init=('XavierFill', {}),
-                    bias_init=const_fill(0.0))
-    fc8d = model.FC(blob_in, prefix + 'fc8d', dim, n_fg, weight_init=('XavierFill', {}),
-                    bias_init=const_fill(0.0))
+    if cfg.WSL.CONTEXT:
+        fc8c, fc8d = add_wsl_context_outputs(model, blob_in, dim, prefix=prefix)
+    else:
+        fc8c = model.FC(blob_in, prefix + 'fc8c', dim, n_fg, weight_init=('XavierFill', {}),
+                        bias_init=const_fill(0.0))
+        fc8d = model.FC(blob_in, prefix + 'fc8d', dim, n_fg, weight_init=('XavierFill', {}),
+                        bias_init=const_fill(0.0))
     _dual_softmax(model, fc8c, fc8d, prefix, '')
     if not model.train:
         # background column = copy of the first foreground score (:58-67)
@@ -23,8 +28,24 @@ def add_wsl_outputs(model, blob_in, dim, prefix=''):
                         split=[1, model.num_classes - 2], axis=1)
         model.net.Concat([prefix + 'rois_bg_pred', prefix + 'rois_pred'],
                          [prefix + 'cls_prob', prefix + 'cls_prob_concat_dims'], axis=1)
+    if cfg.WSL.CONTEXT:
+        blob_in = blob_in[0]       # the refinement branches read the plain roi stream (:69-71)
     if cfg.WSL.OICR:
         add_wsl_oicr_outputs(model, blob_in, dim, prefix=prefix)
+
+
+def add_wsl_context_outputs(model, blobs_in, dim, prefix=''):
+    """blobs_in = [plain, frame, context] streams: classification from the plain stream,
+    detection = fc8d_frame(frame) - fc8d_frame(context), one classifier shared by both."""
+    n_fg = model.num_classes - 1
+    fc8c = model.FC(blobs_in[0], prefix + 'fc8c', dim, n_fg, weight_init=('XavierFill', {}),
+                    bias_init=const_fill(0.0))
+    fc8d_f = model.FC(blobs_in[1], prefix + 'fc8d_frame', dim, n_fg,
+                      weight_init=('XavierFill', {}), bias_init=const_fill(0.0))
+    fc8d_c = model.net.FC([blobs_in[2], prefix + 'fc8d_frame_w', prefix + 'fc8d_frame_b'],
+                          prefix + 'fc8d_context')
+    fc8d = model.net.Sub([fc8d_f, fc8d_c], prefix + 'fc8d')
+    return fc8c, fc8d
 
 
 def add_wsl_oicr_outputs(model, blob_in, dim, prefix=''):
@@ -132,6 +153,8 @@ def _two_fc(model, blob, fc6, drop6, fc7, drop7, dim_in):
 
 
 def add_VGG16_roi_2fc_head(model, blob_in, dim_in, spatial_scale, prefix=''):
+    if cfg.WSL.CONTEXT:
+        return add_VGG16_roi_context_2fc_head(model, blob_in, dim_in, spatial_scale, prefix=prefix)
     roi_size = cfg.FAST_RCNN.ROI_XFORM_RESOLUTION
     feat = model.RoIFeatureTransform(
         blob_in, prefix + 'roi_feat', blob_rois=prefix + 'rois',
@@ -143,6 +166,40 @@ def add_VGG16_roi_2fc_head(model, blob_in, dim_in, spatial_scale, prefix=''):
     out = _two_fc(model, feat, prefix + 'fc6', prefix + 'drop6', prefix + 'fc7', prefix + 'drop7',
                   dim_in * roi_size * roi_size)
     return out, 4096
+
+
+def _two_fc_shared(model, blob, prefix, suffix):
+    """The 2-fc stack on the fc6 / fc7 parameters of the plain stream."""
+    blob = model.net.FC([blob, prefix + 'fc6_w', prefix + 'fc6_b'], prefix + 'fc6' + suffix)
+    blob = model.Relu(blob, prefix + 'fc6' + suffix)
+    blob = DropoutIfTraining(model, blob, prefix + 'drop6' + suffix, 0.5)
+    blob = model.net.FC([blob, prefix + 'fc7_w', prefix + 'fc7_b'], prefix + 'fc7' + suffix)
+    blob = model.Relu(blob, prefix + 'fc7' + suffix)
+    return DropoutIfTraining(model, blob, prefix + 'drop7' + suffix, 0.5)
+
+
+def add_VGG16_roi_context_2fc_head(model, blob_in, dim_in, spatial_scale, prefix=''):
+    """Three streams through one fc6 / fc7: the plain rois (RoIPoolF), their frames and their
+    contexts (RoILoopPool over the 9-column rois RoIContext makes; no argument: ratio 1.8)."""
+    model.net.RoIContext([prefix + 'rois', 'data'], [prefix + 'rois_frame', prefix + 'rois_context'])
+    roi_size = cfg.FAST_RCNN.ROI_XFORM_RESOLUTION
+    blobs_out = []
+    for suffix, method in (('', cfg.FAST_RCNN.ROI_XFORM_METHOD), ('_frame', 'RoILoopPool'),
+                           ('_context', 'RoILoopPool')):
+        feat = model.RoIFeatureTransform(
+            blob_in, prefix + 'roi_feat' + suffix, blob_rois=prefix + 'rois' + suffix,
+            method=method, resolution=roi_size,
+            sampling_ratio=cfg.FAST_RCNN.ROI_XFORM_SAMPLING_RATIO, spatial_scale=spatial_scale)
+        feat = model.net.RoIFeatureBoost([feat, prefix + 'obn_scores'], feat)
+        if cfg.TRAIN.FREEZE_CONV_BODY:
+            feat = model.StopGradient(feat, feat)
+        if suffix == '':
+            out = _two_fc(model, feat, prefix + 'fc6', prefix + 'drop6', prefix + 'fc7',
+                          prefix + 'drop7', dim_in * roi_size * roi_size)
+        else:
+            out = _two_fc_shared(model, feat, prefix, suffix)
+        blobs_out.append(out)
+    return blobs_out, 4096
 
 
 def add_min_entropy_loss(model, pred, label, loss, cpg=None):

@@ -5,6 +5,8 @@ kernels through the C ABI (include/naws.h).
 Custom ops (reference detectron/ops/*):
   RoIFeatureBoost(+Gradient)              roi_feature_boost_op.cc:8-66, schema :70-101
   RoIIoU                                  roi_iou_op.cu:27-84, roi_iou_op.cc:11-24
+  RoIContext                              roi_context_op.cu, schema default context_ratio 1.8
+  RoILoopPool (forward)                   roi_loop_pool_op.cu:31-101      (WSL.CONTEXT)
   WeightedCrossEntropyWithLogits(+Grad.)  cross_entropy_wsl_op.cc:87-180, schema :242-266
   CrossEntropyWithLogits(+Gradient)       cross_entropy_wsl_op.cc:7-85, schema :214-233
   Stat                                    stat_op.cu:24-78, stat_op.cc:11-23
@@ -36,6 +38,19 @@ NawsError = _L.NawsError
 def RoIPoolF(X, R, pooled_h=1, pooled_w=1, spatial_scale=1.0, sampling_ratio=0):
     """-> (Y [n,C,ph,pw], argmax int32).  sampling_ratio is ignored (detector.py:321-329)."""
     return _k.roi_pool_f(X, R, pooled_h, pooled_w, spatial_scale, layout='NCHW', with_argmax=True)
+
+
+def RoIContext(R, X, context_ratio=1.8):
+    """-> (RF [n,9], RC [n,9]): the frame / context rectangles of rois R [n,5], clamped to dims
+    2 / 3 of the image blob X (the builders pass no argument: the ratio is the op default)."""
+    return _k.roi_context(R, X.shape[2], X.shape[3], context_ratio)
+
+
+def RoILoopPool(X, R, pooled_h=1, pooled_w=1, spatial_scale=1.0, sampling_ratio=0):
+    """-> (Y [n,C,ph,pw], argmax int32) for rois R [n,9]; maxima start at 0 and skip the pixels
+    strictly inside the inner rectangle.  Forward only: its gradient needs a trainable conv body."""
+    return _k.roi_loop_pool(X, R, pooled_h, pooled_w, spatial_scale, layout='NCHW',
+                            with_argmax=True)
 
 
 def RoIFeatureBoost(X, S, out=None):
@@ -329,8 +344,8 @@ def FC(X, W, b):
                    bias=_pad_rows4(b))[:, :n].contiguous()
 
 
-def FCGradient(X, W, dY):
-    """-> dW, db, dX."""
+def FCGradient(X, W, dY, need_dx=True):
+    """-> dW, db, dX.  need_dx False: dX is None (no gradient op reads it: the GEMM is skipped)."""
     x2 = X.reshape(X.shape[0], -1)
     n = W.shape[0]
     if n % 4 != 0:
@@ -339,12 +354,12 @@ def FCGradient(X, W, dY):
         dYp[:, :n] = dY
         dW = _k.gemm(dYp, x2, True, False)[:n].contiguous()
         db = _k.colsum(dYp)[:n].contiguous()
-        dX = _k.gemm(dYp, _pad_rows4(W), False, False)
-        return dW, db, dX.view(X.shape)
+        dX = _k.gemm(dYp, _pad_rows4(W), False, False).view(X.shape) if need_dx else None
+        return dW, db, dX
     dW = _k.gemm(dY, x2, True, False)
     db = _k.colsum(dY)
-    dX = _k.gemm(dY, W, False, False)
-    return dW, db, dX.view(X.shape)
+    dX = _k.gemm(dY, W, False, False).view(X.shape) if need_dx else None
+    return dW, db, dX
 
 
 def Dropout(X, ratio=0.5, is_test=False, seed=0):

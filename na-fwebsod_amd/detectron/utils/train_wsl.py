@@ -200,7 +200,9 @@ def begin_iteration_values(executor, model, pg, world, ok=True):
         if k in ws:
             # the op-by-op plan ran the graph's own Accuracy op (OICR: accuracy_cls1..3 too): one
             # value per process there (one image per process)
-            cols.append(ws[k].reshape(-1).double().sum().to(dev) * (n_img / max(ws[k].numel(), 1)))
+            # (the operator form of Accuracy is a host-side metric: a python float)
+            v = torch.as_tensor(ws[k], dtype=torch.float64).reshape(-1)
+            cols.append(v.sum().to(dev) * (n_img / max(v.numel(), 1)))
             names.append(k)
         elif k in fused and fused[k] in ws:
             # the fused engine keeps cls_prob only: top-1 against labels_int32 on the device

@@ -155,6 +155,47 @@ def roi_pool_f(x, rois, pooled_h=7, pooled_w=7, spatial_scale=0.125, boost=None,
     return (y, am) if with_argmax else y
 
 
+def roi_context(rois, max_h, max_w, ratio=1.8):
+    """RoIContext: rois [R,5] -> (frame [R,9], context [R,9]); max_h / max_w are dims 2 / 3 of the
+    padded image blob (include/naws.h: naws_roi_context_fwd)."""
+    _chk(rois, 'rois')
+    if rois.dim() != 2 or rois.shape[1] != 5:
+        raise L.NawsError('naws_roi_context_fwd', L.ERR_SHAPE)
+    r = rois.shape[0]
+    frame = torch.empty((r, 9), device=rois.device, dtype=_f32)
+    context = torch.empty((r, 9), device=rois.device, dtype=_f32)
+    L.call('naws_roi_context_fwd', rois.data_ptr(), r, float(ratio), int(max_h), int(max_w),
+           frame.data_ptr(), context.data_ptr(), _stream())
+    return frame, context
+
+
+def roi_loop_pool(x, rois9, pooled_h=7, pooled_w=7, spatial_scale=0.125, boost=None,
+                  layout='NCHW', with_argmax=False):
+    """RoILoopPool: max pooling over the outer rectangle of rois9 [R,9] minus the pixels strictly
+    inside the inner one, maxima starting at 0 (include/naws.h: naws_roi_loop_pool_fwd)."""
+    _chk(x, 'x'); _chk(rois9, 'rois9')
+    if rois9.dim() != 2 or rois9.shape[1] != 9:
+        raise L.NawsError('naws_roi_loop_pool_fwd', L.ERR_SHAPE)
+    if layout == 'NCHW':
+        n, c, h, w = x.shape
+        lay = L.LAYOUT_NCHW
+    elif layout == 'NHWC':
+        n, h, w, c = x.shape
+        lay = L.LAYOUT_NHWC
+    else:
+        raise L.NawsError('naws_roi_loop_pool_fwd', L.ERR_ARG)
+    r = rois9.shape[0]
+    if boost is not None:
+        _chk(boost, 'boost')
+        assert boost.numel() == r
+    y = torch.empty((r, c, pooled_h, pooled_w), device=x.device, dtype=_f32)
+    am = torch.empty((r, c, pooled_h, pooled_w), device=x.device, dtype=torch.int32) \
+        if with_argmax else None
+    L.call('naws_roi_loop_pool_fwd', x.data_ptr(), lay, n, c, h, w, rois9.data_ptr(), r,
+           _ptr(boost), pooled_h, pooled_w, float(spatial_scale), y.data_ptr(), _ptr(am), _stream())
+    return (y, am) if with_argmax else y
+
+
 def roi_maxmaps(x, m2, m4):
     """The 2x2 / 4x4 block-maxima maps of NHWC features x into m2 / m4 (same shape as x), on the
     current stream (the first half of roi_pool_f_f16x2(hier=True))."""

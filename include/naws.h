@@ -780,6 +780,56 @@ int naws_roi_entropy_fwd(const float* S, const float* C, int n, int num_classes,
                          float* mean, int init, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * f-4  Multi-centre feature loss (WSL.CENTER_LOSS: wsl_heads.py:230-276, :425-431,
+ *      webly_heads.py:199-206).  The reference op selects on the host and synchronises after every
+ *      distance dot; these three entries never synchronise, allocate or copy to the host, use no
+ *      float atomics (bitwise reproducible) and can be captured in a graph.  Shapes: X fp32 [c]
+ *      image labels, P fp32 [n][c] roi scores, F fp32 [n][d] features, CF / dCF fp32 [c][m][d]
+ *      centres / their contribution blob, ndCF fp32 [c][m].  Errors (all three): n < 0 or c, m, d,
+ *      top_k <= 0 -> SHAPE; a null required pointer -> NULL.  n < top_k is no error (every class is
+ *      inactive) and n == 0 succeeds (P, F, dF may then be null).
+ *      workspace: naws_center_loss_workspace_bytes(c, m, top_k) bytes, written by _fwd and read by
+ *      the _bwd that follows it (the selected rois and the active-class count).
+ *      Alignment: 4 bytes is enough everywhere.  The distance kernel reads F and CF 16 bytes at a
+ *      time only when d % 4 == 0 and both pointers are 16-byte aligned, and one float at a time
+ *      otherwise; the two forms sum in different (each fixed) orders, so L may differ in its last
+ *      bits between an aligned and an unaligned call.
+ *
+ * naws_center_loss_fwd — CenterLoss, ref: detectron/ops/center_loss_op.cu:33-278, schema
+ *   center_loss_op.cc:12-32.  A class is active when it is not ignore_label, n >= top_k and its
+ *   label is not below 0.5 (:126-144); it selects top_k rois by repeated strict-'<' argmax over its
+ *   score column (first index wins, -FLT_MAX and NaN never win, :147-172), visits them in ascending
+ *   roi index (:192) and takes the centre with the strictly smallest sum of squared differences
+ *   (:189-219).  -> L fp32 [1] = sum of the chosen distances / active classes / top_k / d / 2 (0
+ *   without an active class), D fp32 [c][top_k][d] = F[r_k] - CF[c][S[c]] (0 for inactive classes),
+ *   S fp32 [c] = the chosen centre (-1 for inactive classes); counts int32 [c][m] (nullable) += 1 at
+ *   [c][S[c]] (the op's display counters).  enabled == 0 is the op past max_iter (:76-78): L = 0,
+ *   D = 0, S = -1.  An active class that cannot find top_k selectable rois makes L NaN (the
+ *   reference fails the net, :161-166).
+ * naws_center_loss_bwd — the gradient half of CenterLossGradient, ref: center_loss_op.cu:466-537.
+ *   dL fp32 [1] -> dF fp32 [n][d] = sum over the (class, k) selections of roi r, in that order, of
+ *   dL / active / top_k / d * D[c][k] (0 elsewhere; all 0 when enabled == 0); with enabled != 0 it
+ *   OVERWRITES dCF / ndCF with this iteration's contribution: ndCF[c][S[c]] = 1,
+ *   dCF[c][S[c]] = -sum_k D[c][k], 0 elsewhere.
+ * naws_center_loss_update — the state half, ref: center_loss_op.cu:340-384, :540-565; call it
+ *   BEFORE naws_center_loss_bwd overwrites the blobs.  acc_dCF += dCF, acc_ndCF += ndCF (the
+ *   previous iteration's contributions, summed over the ranks by the caller); first != 0 zeroes the
+ *   accumulators and both blobs instead (the op's first call).  apply != 0 then sets
+ *   CF -= lr / (int(acc_ndCF) * top_k + 1) * acc_dCF and zeroes the accumulators.
+ * ------------------------------------------------------------------------ */
+int64_t naws_center_loss_workspace_bytes(int c, int m, int top_k);
+int naws_center_loss_fwd(const float* X, const float* P, const float* F, const float* CF, int n,
+                         int c, int m, int d, int top_k, int ignore_label, int enabled,
+                         void* workspace, float* L, float* D, float* S, int32_t* counts,
+                         void* stream);
+int naws_center_loss_bwd(const float* D, const float* S, const float* dL, int n, int c, int m, int d,
+                         int top_k, int enabled, const void* workspace, float* dF, float* dCF,
+                         float* ndCF, void* stream);
+int naws_center_loss_update(float* CF, float* dCF, float* ndCF, float* acc_dCF, float* acc_ndCF,
+                            int c, int m, int d, int top_k, float lr, int first, int apply,
+                            void* stream);
+
+/* ------------------------------------------------------------------------ *
  * f-2  Inference post-processing on the GPU (BASELINE configs[4]: multi-scale TTA).
  *
  * naws_roi_dedup_fwd — per TTA pass p (one workgroup each): project the image boxes into the pass's

@@ -168,6 +168,12 @@ def _defaults():
                                      # rows it does not own after the gather); parameters bit-identical (tests).  A checkpoint
                                      # then needs engine.gather_sharded_state() on every rank (the training loop
                                      # calls it).  Unmeasured on hardware: no multi-GPU node was available
+            # WSL.CENTER_LOSS knobs.  They stand for the reference's WSL.CENTER_LOSS_NUMBER,
+            # WSL.CENTER_LOSS_TOP_K and WSL.CSC_MAX_ITER (config.py there; wsl_heads.py:236, :268-269)
+            # and live here because the reference-format cfg dump omits this node
+            'CENTER_LOSS_NUMBER': 5,       # centres per class
+            'CENTER_LOSS_TOP_K': 10,       # rois per labelled class that are pulled to a centre
+            'CENTER_LOSS_MAX_ITER': 35000,  # the loss switches itself off from this iteration on
             'MFMA_DTYPE': 'fp16x2',  # 'fp32': fp32 MFMA everywhere; 'fp32x3': fc6/fc7 GEMMs as exact
                                      # 3-way bf16 splits on the bf16 MFMA (fp32-accurate, faster);
                                      # 'fp16x2': the same GEMMs as row-scaled 2-way f16 splits on
@@ -181,8 +187,7 @@ def _defaults():
 # Switches that select code outside the hot path: accepted only at their default.
 _OFF_PATH_SWITCHES = (
     'MODEL.MASK_ON', 'MODEL.KEYPOINTS_ON', 'MODEL.RPN_ONLY', 'MODEL.FASTER_RCNN', 'RPN.RPN_ON',
-    'FPN.FPN_ON', 'RETINANET.RETINANET_ON', 'WSL.CPG', 'WSL.CSC', 'WSL.CENTER_LOSS',
-    'WSL.PCL', 'WSL.CMIL',
+    'FPN.FPN_ON', 'RETINANET.RETINANET_ON', 'WSL.CPG', 'WSL.CSC', 'WSL.PCL', 'WSL.CMIL',
 )
 
 cfg = CfgNode(_defaults())

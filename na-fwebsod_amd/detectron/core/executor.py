@@ -71,6 +71,9 @@ class NetExecutor(object):
         sig = _signature(model.net.ops)
         fused_ok = (not force_interpreted and cfg.WEBLY.WEBLY_ON and cfg.WEBLY.ENTROPY and
                     cfg.TRAIN.FREEZE_CONV_BODY and
+                    # the canonical list is built under the current cfg, so it contains CenterLoss
+                    # too: the fused engine does not compute that loss and must not be chosen
+                    not cfg.WSL.CENTER_LOSS and
                     sig == canonical_na_wsddn_signature(model.train, model.num_classes))
         self.plan = 'fused' if fused_ok else 'interpreted'
         self.engine = None
@@ -112,6 +115,8 @@ class NetExecutor(object):
         else:
             for n in self.model.params:
                 self.ws[n] = blobs[n].to(self.device, torch.float32).contiguous()
+                if n in self.model.computed_params:     # op state: SGD never touches it
+                    continue
                 self.ws[n + '_momentum'] = torch.zeros_like(self.ws[n])
                 self.ws[n + '_acmgrad'] = torch.zeros_like(self.ws[n])
 
@@ -121,7 +126,7 @@ class NetExecutor(object):
         out = {}
         for n in self.model.params:
             out[n] = self.ws[n]
-            if with_momentum:
+            if with_momentum and n not in self.model.computed_params:
                 out[n + '_momentum'] = self.ws[n + '_momentum']
         return out
 
@@ -200,6 +205,15 @@ class NetExecutor(object):
             import torch.distributed as dist
             for p in params:
                 dist.all_reduce(ws[self.model.param_to_grad[p]], group=self.pg)
+            # Center_loss_surgery (cpg_utils.py:270-289): the centre contributions are summed over
+            # the ranks; the gradient half of the op takes them in at the next iteration.  Past
+            # max_iter the op no longer rewrites the blobs: summing the stale values again every
+            # iteration would multiply them by `world` until they overflow (the reference's appended
+            # all-reduce does; harmless there too, as nothing reads them), so the sum stops with it.
+            for idx, op in enumerate(self.model.net.ops):
+                if op.type == 'CenterLoss' and self._stats[idx].contributed:
+                    dist.all_reduce(ws[op.inputs[4]], group=self.pg)
+                    dist.all_reduce(ws[op.inputs[5]], group=self.pg)
         for p in params:
             if p not in self._sgd:
                 bias = p in self.model.biases
@@ -303,6 +317,12 @@ class NetExecutor(object):
                                                 num_classes=a.get('num_classes', 20),
                                                 rm_bg=a.get('rm_bg', True))
             ws[out[0]] = self._stats[idx](x[0], x[1])
+        elif t == 'CenterLoss':       # one object per op index: the gradient half shares it
+            if idx not in self._stats:
+                keys = ('top_k', 'update', 'lr', 'display', 'max_iter', 'ignore_label')
+                self._stats[idx] = O.CenterLoss(**{k: a[k] for k in keys if k in a})
+                self._stats[('CenterLoss', out[0])] = self._stats[idx]
+            ws[out[0]], ws[out[1]], ws[out[2]], ws[out[3]] = self._stats[idx].forward(*x[:6])
         elif t == 'BoxWithNMSLimit':
             ws[out[0]], ws[out[1]], ws[out[2]] = O.BoxWithNMSLimit(
                 x[0], x[1], score_thresh=a.get('score_thresh', 0.05), nms=a.get('nms', 0.3),
@@ -365,6 +385,13 @@ class NetExecutor(object):
             res = [O.SoftmaxWithLossNGradient(ws[ins[0]], ws[ins[1]],
                                               ws[ins[2]] if n_in > 2 else None, ws[outs[0]],
                                               gout[1], scale=a.get('scale', 1.0))] + [None] * (n_in - 1)
+        elif t == 'CenterLoss':     # inputs X, P, F, CF, dCF, ndCF; outputs L, D, S, picks
+            # The selection reaches the gradient half through obj.workspace, which forward and
+            # gradient share (one object per op): the `_center_picks` blob is a view of that
+            # workspace, kept in the net for fetching, not read here.
+            obj = self._stats[('CenterLoss', outs[0])]
+            res[2] = obj.gradient(ws[outs[1]], ws[outs[2]], gout[0], ws[ins[2]].shape[0],
+                                  ws[ins[3]], ws[ins[4]], ws[ins[5]])
         else:
             raise NotImplementedError('gradient of ' + t)
         for i, g in enumerate(a['_gin']):

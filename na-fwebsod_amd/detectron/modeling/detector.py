@@ -51,6 +51,7 @@ _GRAD_INPUTS = {
     'Mul': (0, 1), 'Add': (0, 1), 'Sub': (0, 1), 'ReduceSum': (0,), 'AveragedLoss': (0,),
     'WeightedCrossEntropyWithLogits': (0,), 'CrossEntropyWithLogits': (0,),
     'RoIFeatureBoost': (0,), 'MinEntropyLoss': (0,), 'SoftmaxWithLossN': (0,),
+    'CenterLoss': (2,),     # the features only (center_loss_op.cc:55-58): the centres update themselves
 }
 _NO_GRAD = {'StopGradient', 'RoIIoU', 'Stat', 'Accuracy', 'ConstantFill', 'Shape', 'Cast',
             'DequeueBlobs', 'RoILabel', 'RoIEntropy', 'BoxWithNMSLimit', 'RoIContext'}
@@ -68,6 +69,7 @@ class DetectionModelHelper(object):
         self.params, self.weights, self.biases = [], [], []
         self.param_shapes, self.param_inits = {}, {}
         self.param_to_grad = {}
+        self.computed_params = []      # state an op keeps in the net: never trained, no SGD twins
         self.losses, self.metrics = [], []
         self.do_not_update_params, self.gn_params = [], []
         self.roi_data_loader = None
@@ -87,6 +89,15 @@ class DetectionModelHelper(object):
             self.param_inits[name] = init
             self.param_init_net.add(init[0], [], [name], dict(init[1], shape=list(shape)))
         return name
+
+    def create_param(self, param_name, shape, initializer):
+        """A parameter outside any layer helper (ref: ModelHelper.create_param as
+        wsl_heads.py:231-254 uses it): state that an op updates itself.  Saved and broadcast
+        with the others; no gradient op writes `<name>_grad`, so it is never trained and the
+        executor keeps no momentum / accumulated-gradient twin for it."""
+        if param_name not in self.computed_params:
+            self.computed_params.append(param_name)
+        return self._create_param(param_name, shape, initializer, False)
 
     def TrainableParams(self, gpu_id=-1):
         return [p for p in self.params

@@ -42,6 +42,10 @@ def add_webly_losses(model, prefix=''):
                        prefix + 'accuracy_cls' + suffix)
         model.AddLosses([prefix + 'loss_cls' + suffix])
         model.AddMetrics(prefix + 'accuracy_cls' + suffix)
+    if cfg.WSL.CENTER_LOSS:            # webly_heads.py:199-206
+        from detectron.modeling.wsl_heads import add_center_loss
+        loss_gradients.update(add_center_loss('labels_oh', prefix + 'rois_pred', prefix + 'drop7',
+                                              4096, model))
     if cfg.WSL.MIN_ENTROPY_LOSS:       # webly_heads.py:208-214
         from detectron.modeling.wsl_heads import add_min_entropy_loss
         loss_gradients.update(add_min_entropy_loss(model, prefix + 'rois_pred', 'labels_oh',

@@ -3,9 +3,9 @@ add_wsl_outputs (:23-78), add_cls_pred (:213-227), add_cross_entropy_loss (:292-
 add_VGG16_roi_2fc_head (:654-681), DropoutIfTraining (:1259-1267); and, one cfg flag away
 (WSL.OICR): add_wsl_oicr_outputs (:134-156), add_wsl_losses (:375-458),
 add_oicr_losses (:512-560); (WSL.CONTEXT, the ContextLocNet contrastive head):
-add_wsl_context_outputs (:185-209), add_VGG16_roi_context_2fc_head (:684-766).  The PCL / CMIL /
-CSC / center-loss heads of that file are other WSOD methods (cfg switches that core/config.py
-rejects)."""
+add_wsl_context_outputs (:185-209), add_VGG16_roi_context_2fc_head (:684-766); (WSL.CENTER_LOSS, the multi-centre feature loss on
+drop7): add_center_loss (:230-276).  The PCL / CMIL / CSC heads of that file are other WSOD
+methods (cfg switches that core/config.py rejects)."""
 from detectron.core.config import cfg
 from detectron.utils.c2 import const_fill, gauss_fill
 import detectron.utils.blob as blob_utils
@@ -65,7 +65,7 @@ def add_wsl_oicr_outputs(model, blob_in, dim, prefix=''):
 
 def add_wsl_losses(model, prefix=''):
     """The plain WSDDN image-level loss (+ OICR refinement losses): wsl_heads.py:375-458 for the
-    switches the MI355X path accepts (no CPG / CSC / center loss / CMIL / PCL)."""
+    switches the MI355X path accepts (no CPG / CSC / CMIL / PCL)."""
     add_cls_pred(prefix + 'rois_pred', prefix + 'cls_prob', model, prefix='')
     add_cross_entropy_loss(model, prefix + 'cls_prob', 'labels_oh', prefix + 'cross_entropy',
                            weight=None, cpg=None)
@@ -74,6 +74,9 @@ def add_wsl_losses(model, prefix=''):
     model.Accuracy([prefix + 'cls_prob', 'labels_int32'], prefix + 'accuracy_cls')
     model.AddLosses([prefix + 'loss_cls'])
     model.AddMetrics(prefix + 'accuracy_cls')
+    if cfg.WSL.CENTER_LOSS:         # :425-431
+        loss_gradients.update(add_center_loss('labels_oh', prefix + 'rois_pred', prefix + 'drop7',
+                                              4096, model))
     if cfg.WSL.MIN_ENTROPY_LOSS:
         loss_gradients.update(add_min_entropy_loss(model, prefix + 'rois_pred', 'labels_oh',
                                                    prefix + 'loss_entropy', cpg=None))
@@ -200,6 +203,28 @@ def add_VGG16_roi_context_2fc_head(model, blob_in, dim_in, spatial_scale, prefix
             out = _two_fc_shared(model, feat, prefix, suffix)
         blobs_out.append(out)
     return blobs_out, 4096
+
+
+def add_center_loss(label_blob, pred_blob, feature_blob, feature_dims, model):
+    """wsl_heads.py:230-276: the top-k rois of every labelled class are pulled towards the nearest
+    of the class's centres.  The centres (`center_feature`, GaussianFill) and the two in-place
+    contribution blobs (`center_feature_g`, `center_feature_n_u`, zero) are parameters of the net -
+    saved with it, broadcast from rank 0 - that no gradient reaches: the op's gradient half moves
+    the centres itself.  `_center_picks` is the hidden selection the gradient half reuses."""
+    n_fg = model.num_classes - 1
+    m = cfg.NAWS.CENTER_LOSS_NUMBER
+    CF = model.create_param('center_feature', [n_fg, m, feature_dims], ('GaussianFill', {}))
+    dCF = model.create_param('center_feature_g', [n_fg, m, feature_dims],
+                             ('ConstantFill', {'value': 0.0}))
+    ndCF = model.create_param('center_feature_n_u', [n_fg, m], ('ConstantFill', {'value': 0.0}))
+    loss_center = model.net.CenterLoss(
+        [label_blob, pred_blob, feature_blob, CF, dCF, ndCF],
+        ['loss_center', 'D', 'S', '_center_picks'],
+        max_iter=cfg.NAWS.CENTER_LOSS_MAX_ITER, top_k=cfg.NAWS.CENTER_LOSS_TOP_K,
+        display=int(1280 / cfg.NUM_GPUS), update=int(128 / cfg.NUM_GPUS))[0]
+    loss_gradients = get_loss_gradients_weighted(model, [loss_center], 0.4096)
+    model.AddLosses(['loss_center'])
+    return loss_gradients
 
 
 def add_min_entropy_loss(model, pred, label, loss, cpg=None):

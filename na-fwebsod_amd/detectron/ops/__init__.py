@@ -13,6 +13,7 @@ Custom ops (reference detectron/ops/*):
   RoILabel                                roi_label_op.cc:10-123          (WSL.OICR)
   SoftmaxWithLossN(+Gradient)             softmax_with_loss_n_op.cc:152-357
   RoIEntropy, BoxWithNMSLimit (gate form) roi_entropy_op.cu:24-142, webly_heads.py:238-248
+  CenterLoss(+Gradient)                   center_loss_op.cu:33-568        (WSL.CENTER_LOSS)
   ACMWeightDecayMomentumSGDUpdate         acm_weightdecay_momentum_sgd_op.h:48-112
 Caffe2 built-ins used by the path (pytorch v1.3.0 caffe2/operators, restated): RoIPoolF,
 Conv, Relu, MaxPool, FC, Dropout, Softmax, Transpose, Add/Sub/Mul/Div (numpy-style
@@ -204,6 +205,76 @@ class RoIEntropy(object):
             self.printer(''.join('  %g' % v for v in self.mean.cpu().tolist()))
             self.init = True
         return e
+
+
+class CenterLoss(object):
+    """detectron/ops/center_loss_op.cu:33-568 (schema center_loss_op.cc:12-69, state
+    center_loss_op.h): the multi-centre feature loss behind WSL.CENTER_LOSS.  One object is both
+    halves of the op pair, as they share the selection:
+
+      forward(X [1,c], P [n,c], F [n,d], CF [c,m,d], dCF, ndCF) -> (L [], D [c,top_k,d], S [c], picks)
+      gradient(D, S, picks, dL, n, CF, dCF, ndCF) -> dF [n,d]; CF / dCF / ndCF change in place.
+
+    State = the two iteration counters (host integers), the gradient op's private accumulators
+    and the display counters (device).  The reference selects on the host and blocks after every
+    distance dot; nothing here reads the device back except the display line, printed at call 1 and
+    every `display` calls."""
+
+    def __init__(self, top_k=10, update=128, lr=0.5, display=1280, max_iter=0, ignore_label=-1,
+                 printer=print):
+        self.top_k, self.update, self.lr = int(top_k), int(update), float(lr)
+        self.display, self.max_iter, self.ignore_label = int(display), int(max_iter), int(ignore_label)
+        self.printer = printer
+        self.cur_iter = self.cur_iter_grad = 0
+        self.init_grad = True
+        self.contributed = False      # the last gradient call rewrote dCF / ndCF
+        self.acc_dCF = self.acc_ndCF = self.counts = self.accum_loss = self.workspace = None
+
+    def forward(self, X, P, F, CF, dCF=None, ndCF=None):
+        # dCF / ndCF are inputs of the op so that the net orders it with their writers
+        # (center_loss_op.cc:12-32); the forward half does not read them (:33-278)
+        c, m, _ = CF.shape
+        if self.counts is None:
+            self.counts = torch.zeros((c, m), device=CF.device, dtype=torch.int32)
+            self.accum_loss = torch.zeros((1, 1), device=CF.device, dtype=torch.float32)
+            self.workspace = _k.center_loss_workspace(c, m, self.top_k, CF.device)
+        enabled = self.cur_iter < self.max_iter
+        loss, D, S, ws = _k.center_loss(X.contiguous().reshape(-1), P.contiguous(), F.contiguous(),
+                                        CF, self.top_k, self.ignore_label, enabled,
+                                        workspace=self.workspace, counts=self.counts)
+        picks = _k.center_loss_picks(ws, c, self.top_k)
+        if not enabled:                                 # :76-78: no counter, no display
+            return loss.reshape(()), D, S, picks
+        _k.binary(_L.BIN_ADD, self.accum_loss, loss.reshape(1, 1), out=self.accum_loss)
+        self.cur_iter += 1
+        if self.cur_iter % self.display == 0 or self.cur_iter == 1:
+            acc = float(self.accum_loss.item())
+            self.printer('CenterLoss #iter_: %d #loss_: %g AVE loss: %g' % (
+                self.cur_iter, acc, float(np.float32(acc) / np.float32(self.display))))
+            cnt = self.counts.cpu().tolist()
+            asum = CF.abs().sum(dim=2).cpu().tolist()
+            for row, sums in zip(cnt, asum):
+                self.printer(''.join('%d\t' % v for v in row) + '\t' +
+                             ''.join('%g\t' % v for v in sums))
+            self.printer('')
+            self.accum_loss.zero_()
+            self.counts.zero_()
+        return loss.reshape(()), D, S, picks
+
+    def gradient(self, D, S, dL, n, CF, dCF, ndCF):
+        if self.acc_dCF is None:
+            self.acc_dCF, self.acc_ndCF = torch.zeros_like(dCF), torch.zeros_like(ndCF)
+        enabled = self.cur_iter_grad < self.max_iter
+        if enabled:
+            self.cur_iter_grad += 1
+            # the accumulators read last iteration's blobs before this iteration overwrites them
+            _k.center_loss_update(CF, dCF, ndCF, self.acc_dCF, self.acc_ndCF, self.top_k, self.lr,
+                                  first=self.init_grad,
+                                  apply=self.cur_iter_grad % self.update == 0)
+            self.init_grad = False
+        self.contributed = enabled
+        return _k.center_loss_grad(D, S, dL.reshape(1).contiguous(), n, self.workspace, dCF, ndCF,
+                                   enabled=enabled)
 
 
 def BoxWithNMSLimit(scores, boxes, score_thresh=0.05, nms=0.3, detections_per_im=100):

@@ -69,6 +69,9 @@ PROTOTYPES = {
     'naws_softmax_with_loss_n_fwd': [p, p, p, i32, i32, f32, p, p, p, p],
     'naws_softmax_with_loss_n_bwd': [p, p, p, p, i32, i32, f32, p, p, p],
     'naws_roi_entropy_fwd': [p, p, i32, i32, i32, p, p, i32, p],
+    'naws_center_loss_fwd': [p, p, p, p, i32, i32, i32, i32, i32, i32, i32, p, p, p, p, p, p],
+    'naws_center_loss_bwd': [p, p, p, i32, i32, i32, i32, i32, i32, p, p, p, p, p],
+    'naws_center_loss_update': [p, p, p, p, p, i32, i32, i32, i32, f32, i32, i32, p],
     'naws_roi_dedup_fwd': [p, p, i32, i32, p, f32, p, p, p, p, p, p],
     'naws_tta_accumulate': [p, p, i32, i32, i32, p, p],
     'naws_tta_finish': [p, i64, i32, p],
@@ -151,6 +154,7 @@ SPECIAL = {
     'naws_nms_workspace_bytes': ([i32, i32], i64),
     'naws_roi_label_workspace_bytes': ([i32, i32, i32], i64),
     'naws_softmax_with_loss_n_workspace_floats': ([i32], i64),
+    'naws_center_loss_workspace_bytes': ([i32, i32, i32], i64),
     'naws_roi_pool_workspace_floats': ([i32, i32, i32, i32], i64),
     'naws_winograd_f32x3_workspace_floats': ([i32, i32, i32, i32, i32, i32], i64),
     'naws_winograd_f16x2_workspace_floats': ([i32, i32, i32, i32, i32, i32], i64),

@@ -1411,6 +1411,95 @@ def roi_entropy(s, c, num_classes, rm_bg=True, mean=None, init=True):
     return e
 
 
+def center_loss_workspace(c, m, top_k, device):
+    """The int32 scratch naws_center_loss_fwd fills and naws_center_loss_bwd reads."""
+    return torch.empty((max(L.load().naws_center_loss_workspace_bytes(c, m, top_k), 16) // 4,),
+                       device=device, dtype=torch.int32)
+
+
+def _center_workspace_ok(ws, c, m, top_k):
+    """A workspace sized for other (c, m, top_k) would be written or read out of bounds."""
+    return ws.is_contiguous() and \
+        ws.numel() * 4 >= L.load().naws_center_loss_workspace_bytes(int(c), int(m), int(top_k))
+
+
+def _center_dims(p, f, cf):
+    if p.dim() != 2 or f.dim() != 2 or cf.dim() != 3 or p.shape[0] != f.shape[0] or \
+            cf.shape[0] != p.shape[1] or cf.shape[2] != f.shape[1]:
+        raise L.NawsError('naws_center_loss_fwd', L.ERR_SHAPE)      # ENFORCE sites .cu:41-55
+    return p.shape[0], cf.shape[0], cf.shape[1], cf.shape[2]
+
+
+def center_loss(x, p, f, cf, top_k=10, ignore_label=-1, enabled=True, workspace=None, counts=None):
+    """CenterLoss forward -> (L [1], D [c,top_k,d], S [c], workspace).  `workspace`
+    (center_loss_workspace) carries the selection to center_loss_grad; `counts` (int32 [c,m],
+    optional) accumulates how often each centre was chosen.  No host synchronisation."""
+    _chk(x, 'X'); _chk(p, 'P'); _chk(f, 'F'); _chk(cf, 'CF')
+    n, c, m, d = _center_dims(p, f, cf)
+    if x.numel() != c:
+        raise L.NawsError('naws_center_loss_fwd', L.ERR_SHAPE)
+    if int(top_k) <= 0:
+        raise L.NawsError('naws_center_loss_fwd', L.ERR_SHAPE)
+    dev = p.device
+    ws = workspace if workspace is not None else center_loss_workspace(c, m, top_k, dev)
+    _chk(ws, 'workspace', torch.int32)
+    if counts is not None:
+        _chk(counts, 'counts', torch.int32)
+    if not _center_workspace_ok(ws, c, m, top_k) or \
+            (counts is not None and (tuple(counts.shape) != (c, m) or not counts.is_contiguous())):
+        raise L.NawsError('naws_center_loss_fwd', L.ERR_SHAPE)
+    loss = torch.empty((1,), device=dev, dtype=_f32)
+    dd = torch.empty((c, int(top_k), d), device=dev, dtype=_f32)
+    s = torch.empty((c,), device=dev, dtype=_f32)
+    L.call('naws_center_loss_fwd', x.data_ptr(), p.data_ptr(), f.data_ptr(), cf.data_ptr(), n, c, m,
+           d, int(top_k), int(ignore_label), int(bool(enabled)), ws.data_ptr(), loss.data_ptr(),
+           dd.data_ptr(), s.data_ptr(), _ptr(counts), _stream())
+    return loss, dd, s, ws
+
+
+def center_loss_picks(workspace, c, top_k):
+    """The selected rois of the last center_loss call on `workspace`: int32 [c, top_k] in ascending
+    roi index, -1 rows for inactive classes (a view)."""
+    return workspace[:c * top_k].view(c, top_k)
+
+
+def center_loss_grad(d_, s, dl, n, workspace, dcf, ndcf, enabled=True, out=None):
+    """The gradient half of CenterLossGradient -> dF [n,d]; overwrites dcf / ndcf in place with
+    this iteration's contribution (call center_loss_update first: it reads the old ones)."""
+    _chk(d_, 'D'); _chk(s, 'S'); _chk(dl, 'dL'); _chk(dcf, 'dCF'); _chk(ndcf, 'ndCF')
+    _chk(workspace, 'workspace', torch.int32)
+    c, top_k, d = d_.shape
+    if dcf.dim() != 3 or dcf.shape[0] != c or dcf.shape[2] != d or s.numel() != c or \
+            tuple(ndcf.shape) != tuple(dcf.shape[:2]) or dl.numel() != 1:
+        raise L.NawsError('naws_center_loss_bwd', L.ERR_SHAPE)      # ENFORCE sites .cu:290-309
+    m = dcf.shape[1]
+    df = out if out is not None else torch.empty((int(n), d), device=d_.device, dtype=_f32)
+    _chk(df, 'dF')
+    if int(n) < 0 or top_k <= 0 or not _center_workspace_ok(workspace, c, m, top_k) or \
+            tuple(df.shape) != (int(n), d) or not df.is_contiguous():
+        raise L.NawsError('naws_center_loss_bwd', L.ERR_SHAPE)
+    L.call('naws_center_loss_bwd', d_.data_ptr(), s.data_ptr(), dl.data_ptr(), int(n), c, m, d,
+           top_k, int(bool(enabled)), workspace.data_ptr(), df.data_ptr(), dcf.data_ptr(),
+           ndcf.data_ptr(), _stream())
+    return df
+
+
+def center_loss_update(cf, dcf, ndcf, acc_dcf, acc_ndcf, top_k=10, lr=0.5, first=False, apply=False):
+    """The state half of CenterLossGradient, in place: the accumulators take the (rank-summed)
+    previous contribution held in dcf / ndcf (`first`: everything is zeroed instead); `apply` moves
+    the centres by the accumulated contribution and zeroes the accumulators."""
+    for t, nm in ((cf, 'CF'), (dcf, 'dCF'), (ndcf, 'ndCF'), (acc_dcf, 'acc_dCF'),
+                  (acc_ndcf, 'acc_ndCF')):
+        _chk(t, nm)
+    if cf.dim() != 3 or dcf.shape != cf.shape or acc_dcf.shape != cf.shape or \
+            tuple(ndcf.shape) != tuple(cf.shape[:2]) or acc_ndcf.shape != ndcf.shape:
+        raise L.NawsError('naws_center_loss_update', L.ERR_SHAPE)
+    c, m, d = cf.shape
+    L.call('naws_center_loss_update', cf.data_ptr(), dcf.data_ptr(), ndcf.data_ptr(),
+           acc_dcf.data_ptr(), acc_ndcf.data_ptr(), c, m, d, int(top_k), float(lr),
+           int(bool(first)), int(bool(apply)), _stream())
+
+
 # ----------------------------------------------------------------------------
 # inference post-processing on the device (SURVEY.md 8 f-2)
 # ----------------------------------------------------------------------------

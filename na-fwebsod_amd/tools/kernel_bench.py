@@ -261,6 +261,25 @@ def main():
             del conv5, t
         print('10-pass TTA (5 scales x flip): %.1f ms per image forward, %.1f ms with paired flips' % (
             tot, tot_pair))
+    if 'center' in what:
+        # WSL.CENTER_LOSS at one image's worth of proposals: R = 2000, C = 20, M = 5, top_k = 10,
+        # Dm = 4096, half the classes labelled (the worst case of the test inputs)
+        n, c, m, top_k, d = a.rois, 20, 5, 10, 4096
+        x = (torch.arange(c, device=dev) % 2 == 0).float()
+        p, f, cf = rnd(n, c), rnd(n, d), rnd(c, m, d)
+        dcf, ndcf = torch.zeros((c, m, d), device=dev), torch.zeros((c, m), device=dev)
+        acc_d, acc_n = torch.zeros_like(dcf), torch.zeros_like(ndcf)
+        ws = ops.center_loss_workspace(c, m, top_k, dev)
+        dl = torch.full((1,), 0.4096, device=dev)
+        df = torch.empty((n, d), device=dev)
+        ms_f = timeit(lambda: ops.center_loss(x, p, f, cf, top_k, workspace=ws), a.iters)
+        _l, dd, ss, _w = ops.center_loss(x, p, f, cf, top_k, workspace=ws)
+        ms_b = timeit(lambda: ops.center_loss_grad(dd, ss, dl, n, ws, dcf, ndcf, out=df), a.iters)
+        ms_u = timeit(lambda: ops.center_loss_update(cf, dcf, ndcf, acc_d, acc_n, top_k, 0.5,
+                                                     apply=True), a.iters)
+        print('center_loss R=%d C=%d M=%d top_k=%d Dm=%d: fwd %7.3f ms (4 launches), bwd %7.3f ms '
+              '(dF %.0f MB written: %.0f GB/s), update %7.3f ms' % (
+                  n, c, m, top_k, d, ms_f, ms_b, df.numel() * 4 / 1e6, df.numel() * 4 / ms_b / 1e6, ms_u))
     if 'roi' in what:
         import numpy as np
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..',

@@ -394,7 +394,12 @@ __global__ void unary_kernel(int op, const float* __restrict__ X, int64_t n, flo
     const float x = X[i];
     float y;
     switch (op) {
-      case NAWS_UN_LOG: y = logf(x); break;
+      // (logf compiles to v_log_f32 x ln 2: the hardware log2's own ulp plus the product's
+      // roundings reached 2.1 ulp; the double log rounds once.  Measured on an MI355X: as fast
+      // as SCALE at 2^20 elements (8 us, launch-bound), 2.1-2.3 TB/s against SCALE's 4.7-6.1
+      // from 2^24 up - no longer at the memory roofline there; the one caller is the op-by-op
+      // Log on [R, C] blobs)
+      case NAWS_UN_LOG: y = (float)log((double)x); break;
       case NAWS_UN_SCALE: y = x * a; break;
       case NAWS_UN_REPLACE_NAN: y = isnan(x) ? a : x; break;
       case NAWS_UN_LEAKY_RELU: y = x >= 0.f ? x : a * x; break;

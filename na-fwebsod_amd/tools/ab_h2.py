@@ -7,6 +7,11 @@ output entries.  (Perf deltas between separate runs or boxes are not comparable:
 spread - cdna_hip_programming.md rule 24.)
 
     python tools/ab_h2.py --variants 0 7 [--rounds 9]
+    python tools/ab_h2.py --variants 0 18 --only fc      # pipelined K loop (default) vs two-phase
+
+h2 = 18 is the two-phase K loop of the 256 x 256 form, 19 the same with that form forced (as 5 forces
+it with the default loop); both exist in the default build.  'fc7 dgrad' is the unbatched
+4000 x 4096 x 4096 product.
 """
 import argparse
 import ctypes as C
@@ -63,6 +68,7 @@ def main():
              ('fc6 wgrad', (8192, kr), (24576, kr), None),
              ('fc7 fwd  ', (2, R, 4096), (2, 4096, 4096), None),
              ('fc7 wgrad', (2, 4096, kr), (2, 4096, kr), None),
+             ('fc7 dgrad', (R, 4096), (4096, 4096), None),
              ('wino conv4_2', (16, 2394, 512), (16, 512, 512), None),
              ('wino conv4_1', (16, 2394, 256), (16, 512, 256), None)]
     g = torch.Generator(device=dev).manual_seed(1)

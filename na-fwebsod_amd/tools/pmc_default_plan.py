@@ -21,8 +21,11 @@ LABEL = {('gemm_h2_btr_kernel<256, 256, 4, 2, true', '1572864', None): 'fc6 wgra
 
 
 def label_of(key):
+    # (the software-pipelined siblings carry their two-phase template's label)
+    name = key[0].replace('gemm_x3_m16p_kernel', 'gemm_x3_m16_kernel').replace(
+        'gemm_h2_btrp_kernel', 'gemm_h2_btr_kernel')
     for (pre, grid, work), text in LABEL.items():
-        if key[0].startswith(pre) and (grid is None or key[1] == grid) and \
+        if name.startswith(pre) and (grid is None or key[1] == grid) and \
                 (work is None or abs(key[2] - work) <= 0.06 * work):
             return text
     return None

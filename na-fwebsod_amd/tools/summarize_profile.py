@@ -78,7 +78,14 @@ def template_match(prefix, kernel_name):
     """True when `kernel_name` is an instance of the template prefix: the prefix must be followed
     by `,` (more template arguments), `>` (none), `(` (the kernel is not a template) or `<` (the prefix
     is a bare template name)."""
-    return re.search(re.escape(prefix) + r'\s*[,>(<]', kernel_name) is not None
+    return re.search(re.escape(prefix) + r'\s*[,>(<]', same_template(kernel_name)) is not None
+
+
+def same_template(kernel_name):
+    """The software-pipelined siblings (gemm_x3_m16p_kernel, gemm_h2_btrp_kernel: the same tile,
+    template arguments and problem behind another K loop) count as their two-phase templates."""
+    return kernel_name.replace('gemm_x3_m16p_kernel', 'gemm_x3_m16_kernel').replace(
+        'gemm_h2_btrp_kernel', 'gemm_h2_btr_kernel')
 
 
 def _find(d, pat):

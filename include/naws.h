@@ -91,6 +91,59 @@ int naws_nchw_to_nhwc(const float* X, int N, int C, int H, int W, float* Y, void
 int naws_nhwc_to_nchw(const float* X, int N, int H, int W, int C, float* Y, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * a-1b  Backward of the conv body (TRAIN.FREEZE_CONV_BODY False, op-by-op
+ *       plan)   ref: Caffe2 ConvGradient / MaxPoolGradient (pytorch v1.3.0
+ *       caffe2/operators/conv_op_impl.h, pool_gradient_op.cc) as
+ *       detectron/modeling/VGG16.py:9-48 makes them for conv3_1..conv5_3.
+ * No new MFMA kernel: the data gradient is naws_conv3x3_nhwc_fwd on dY with
+ * the weight packed below, the weight gradient is nine strided products on
+ * naws_gemm_f32_splitk.  Common errors: a non-positive dim -> SHAPE; a
+ * stride or dilation other than 1 / 2 -> ARG; Cin or Cout % 32 != 0 ->
+ * UNSUPPORTED; a missing pointer -> NULL.
+ * ------------------------------------------------------------------------ */
+
+/* MaxPoolGradient of naws_maxpool2x2_nhwc_fwd (same N, H, W, C, stride; X its
+ * input, Y [N,Ho,Wo,C] its output, dY the gradient of Y) -> dX [N,H,W,C].
+ * Gather form, no atomics: dX[h,w] = the sum of dY over the (up to four)
+ * windows that contain (h,w) and SELECT it, visited in ascending window index
+ * yo*Wo+xo, starting from 0 - bit-reproducible.  The forward takes
+ * fmaxf(fmaxf(a,b), fmaxf(d,e)) over a = (y,x), b = (y,x+1), d = (y+1,x),
+ * e = (y+1,x+1); the selected element is the FIRST of a, b, d, e that equals
+ * the stored maximum (a window tied at 0 after ReLU gives its gradient to a;
+ * a NaN is never selected).  Pixels beyond the last full window (odd H or W
+ * at stride 2) get 0.  C % 4 != 0 or a pointer not 16-byte aligned -> ARG. */
+int naws_maxpool2x2_nhwc_bwd(const float* X, const float* Y, const float* dY, int N, int H,
+                             int W, int C, int stride, float* dX, void* stream);
+
+/* The packed operand of naws_conv3x3_nhwc_fwd for the DATA gradient of a
+ * 3x3, stride-1, pad == dilation convolution with weight W_oihw
+ * [Cout,Cin,3,3]: dX = conv3x3(dY, W', same dilation, bias NULL, relu 0) with
+ * W'[ci,co,ky,kx] = W[co,ci,2-ky,2-kx], packed [Cin][ky][kx][Cout] (the roles
+ * of Cin and Cout swap in that call: Cin = this Cout, Cout = this Cin). */
+int naws_conv3x3_dgrad_pack_weight(const float* W_oihw, int Cout, int Cin, float* W_packed,
+                                   void* stream);
+
+/* WEIGHT and bias gradient of the same convolution: X [N,H,W,Cin] and dY
+ * [N,H,W,Cout] (NHWC) -> dW [Cout,Cin,3,3] (OIHW, the blob layout) and
+ * db [Cout] = sum of dY over the pixels:
+ *   dW[co,ci,ky,kx] = sum_{n,y,x} dY[n,y,x,co] * X[n, y+(ky-1)d, x+(kx-1)d, ci]
+ * (zero outside the image).  X and dY are staged into `workspace` zero-padded
+ * on ONE geometry - row width W+2d, d zero rows above and below every image -
+ * so that tap (ky,kx) is a plain product of two row-strided views, the view of
+ * X starting ((ky-1)(W+2d) + (kx-1)) d pixel rows after the view of dY (all
+ * offsets are multiples of Cin >= 32 floats: the GEMM's 16-byte rule holds).
+ * The nine products run on naws_gemm_f32_splitk (fp32 MFMA; K = the pixel
+ * rows, the slices summed in a fixed order, so dW is bit-reproducible), three
+ * per batched call, and one kernel writes OIHW; db is naws_colsum_f32.
+ * workspace: naws_conv3x3_nhwc_wgrad_workspace_floats floats (0 for arguments
+ * the entry refuses), caller-owned, 16-byte aligned like X and dY (-> ARG). */
+int64_t naws_conv3x3_nhwc_wgrad_workspace_floats(int N, int H, int W, int Cin, int Cout,
+                                                 int dilation);
+int naws_conv3x3_nhwc_wgrad(const float* X, const float* dY, int N, int H, int W, int Cin,
+                            int Cout, int dilation, float* workspace, float* dW, float* db,
+                            void* stream);
+
+/* ------------------------------------------------------------------------ *
  * a-2 / a-3  RoIPoolF (+ RoIFeatureBoost)
  *   ref: detectron/modeling/detector.py:268-331 (op emission),
  *        detectron/ops/roi_loop_pool_op.cu:31-101 (in-tree statement of the
@@ -106,6 +159,21 @@ int naws_roi_pool_f_fwd(const float* X, int layout, int N, int C, int H, int W,
                         const float* rois, int R, const float* boost,
                         int pooled_h, int pooled_w, float spatial_scale,
                         float* Y, int32_t* argmax, void* stream);
+
+/* RoIPoolFGradient (ref: Caffe2 roi_pool_op.cu RoIPoolFBackward as
+ * detectron/ops/roi_pool_f_op.cu states it): dY and argmax [R,C,ph,pw] as
+ * naws_roi_pool_f_fwd wrote them, rois [R,5] -> dX, the gradient of X in the
+ * given layout:  dX[b, c, argmax] += dY[r, c, ph, pw]  with b = rois[r,0];
+ * argmax -1 (an empty bin) contributes nothing.  dX is zero-filled by the
+ * entry (also when R == 0).  The sums run on no-return float atomic adds
+ * (global_atomic_add_f32), as in the reference kernel: rois that share a
+ * pixel add in no fixed order, so dX is reproducible to rounding, not to the
+ * bit.  An argmax outside [0, H*W) or a batch index outside [0, N) is
+ * skipped.  The gradient of the fused boost is naws_roi_feature_boost_bwd.
+ * Errors: R<0, N/C/H/W/ph/pw<=0 -> SHAPE; layout unknown -> ARG. */
+int naws_roi_pool_f_bwd(const float* dY, const int32_t* argmax, const float* rois, int R,
+                        int layout, int N, int C, int H, int W, int pooled_h, int pooled_w,
+                        float* dX, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * RoIContext / RoILoopPool: the contextual WSDDN head (WSL.CONTEXT)

@@ -352,6 +352,17 @@ class NetExecutor(object):
             dW, db, dX = O.FCGradient(ws[ins[0]], ws[ins[1]], gout[0].contiguous(),
                                       need_dx=a['_gin'][0] is not None)
             res = [dX, dW, db]
+        elif t == 'Conv':
+            dW, db, dX = O.ConvGradient(ws[ins[0]], ws[ins[1]], gout[0], kernel=a.get('kernel', 3),
+                                        pad=a.get('pad', 1), stride=a.get('stride', 1),
+                                        dilation=a.get('dilation', 1),
+                                        need_dx=a['_gin'][0] is not None)
+            res = [dX, dW, db]
+        elif t == 'MaxPool':
+            res = [O.MaxPoolGradient(ws[ins[0]], ws[outs[0]], gout[0], kernel=a['kernel'],
+                                     pad=a['pad'], stride=a['stride'])]
+        elif t == 'RoIPoolF':      # outputs Y, argmax: the forward's own selection
+            res = [O.RoIPoolFGradient(ws[ins[0]], ws[ins[1]], ws[outs[1]], gout[0]), None]
         elif t == 'Relu':
             res = [O.ReluGradient(ws[outs[0]], gout[0])]
         elif t == 'Dropout':

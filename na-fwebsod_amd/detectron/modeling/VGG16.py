@@ -1,7 +1,8 @@
 """VGG-16 conv5 body of the WSL path.  Mirrors detectron/modeling/VGG16.py:9-48
 (`add_VGG16_conv5_body_origin`): thirteen 3x3 conv + in-place ReLU, k2s2 max-pools after
 blocks 1-3, and with WSL.DILATION == 2 a stride-1 pool4 followed by dilation-2 conv5_x
-(feature stride 8); FREEZE_AT == 2 stops gradients at pool2."""
+(feature stride 8); FREEZE_AT == 2 stops gradients at pool2 - the only value a trainable body
+(TRAIN.FREEZE_CONV_BODY False) accepts."""
 from detectron.core.config import cfg
 
 _BLOCKS = (
@@ -21,6 +22,11 @@ def _conv_relu(model, blob_in, name, dim_in, dim_out, pad, dilation):
 
 
 def add_VGG16_conv5_body_origin(model):
+    if model.train and not cfg.TRAIN.FREEZE_CONV_BODY and cfg.TRAIN.FREEZE_AT != 2:
+        # conv1_1 has 3 input channels and no weight-gradient form; the body trains from conv3_1
+        raise NotImplementedError('TRAIN.FREEZE_AT: {} with TRAIN.FREEZE_CONV_BODY: False is not '
+                                  'on the hot path: the trainable body needs TRAIN.FREEZE_AT: 2 '
+                                  '(conv3_1 and up)'.format(cfg.TRAIN.FREEZE_AT))
     blob = 'data'
     for idx, dims in _BLOCKS:
         for j in range(1, len(dims)):

@@ -52,6 +52,8 @@ _GRAD_INPUTS = {
     'WeightedCrossEntropyWithLogits': (0,), 'CrossEntropyWithLogits': (0,),
     'RoIFeatureBoost': (0,), 'MinEntropyLoss': (0,), 'SoftmaxWithLossN': (0,),
     'CenterLoss': (2,),     # the features only (center_loss_op.cc:55-58): the centres update themselves
+    # the trainable conv body (TRAIN.FREEZE_CONV_BODY False): features only for the two poolings
+    'Conv': (0, 1, 2), 'MaxPool': (0,), 'RoIPoolF': (0,),
 }
 _NO_GRAD = {'StopGradient', 'RoIIoU', 'Stat', 'Accuracy', 'ConstantFill', 'Shape', 'Cast',
             'DequeueBlobs', 'RoILabel', 'RoIEntropy', 'BoxWithNMSLimit', 'RoIContext'}
@@ -179,9 +181,10 @@ class DetectionModelHelper(object):
         loss blob to the blob holding its gradient seed (blob.py:167-173).  Blobs consumed by
         several ops accumulate (`<name>_grad` summed), parameters shared by several FC ops
         (the context head's fc6 / fc7 / fc8d_frame) included; StopGradient and the ops in
-        _NO_GRAD cut the flow, so nothing upstream of `roi_feat` / `conv5_3` or inside the
-        entropy gate gets a gradient op.  An FC whose input comes from such an
-        op (or from outside the net) emits no input gradient: nothing would read it."""
+        _NO_GRAD cut the flow, so nothing upstream of `roi_feat` / `conv5_3` (frozen body) or of
+        pool2 (TRAIN.FREEZE_CONV_BODY False, FREEZE_AT 2) or inside the entropy gate gets a
+        gradient op.  An FC or Conv whose input comes from such an op (or from
+        outside the net) emits no input gradient: nothing would read it."""
         grad_of = {str(k): str(v) for k, v in loss_gradients.items()}
         ops = []
         producer = {}           # forward index of an op -> {input blob: type of its latest producer}
@@ -205,9 +208,11 @@ class DetectionModelHelper(object):
             gin = []
             for i, name in enumerate(op.inputs):
                 gin.append(name + '_grad' if i in _GRAD_INPUTS[op.type] else None)
-            if op.type == 'FC' and (producer[idx][op.inputs[0]] is None or
-                                    producer[idx][op.inputs[0]] in _NO_GRAD):
-                gin[0] = None       # dX = dY W behind StopGradient: a GEMM nobody consumes
+            if op.type in ('FC', 'Conv') and (producer[idx][op.inputs[0]] is None or
+                                              producer[idx][op.inputs[0]] in _NO_GRAD):
+                # dX behind StopGradient (fc6 over a frozen body, conv3_1 over pool2): a GEMM /
+                # a convolution nobody consumes
+                gin[0] = None
             # in-place ops (Relu fc6->fc6): the output's gradient is consumed here
             for o in op.outputs:
                 if o in op.inputs:

@@ -15,9 +15,9 @@ Custom ops (reference detectron/ops/*):
   RoIEntropy, BoxWithNMSLimit (gate form) roi_entropy_op.cu:24-142, webly_heads.py:238-248
   CenterLoss(+Gradient)                   center_loss_op.cu:33-568        (WSL.CENTER_LOSS)
   ACMWeightDecayMomentumSGDUpdate         acm_weightdecay_momentum_sgd_op.h:48-112
-Caffe2 built-ins used by the path (pytorch v1.3.0 caffe2/operators, restated): RoIPoolF,
-Conv, Relu, MaxPool, FC, Dropout, Softmax, Transpose, Add/Sub/Mul/Div (numpy-style
-broadcast), ReduceSum, Log, Scale, ReplaceNaN, MatMul, LeakyRelu, Clip, ConstantFill,
+Caffe2 built-ins used by the path (pytorch v1.3.0 caffe2/operators, restated): RoIPoolF
+(+Gradient), Conv(+Gradient), Relu, MaxPool(+Gradient), FC, Dropout, Softmax, Transpose,
+Add/Sub/Mul/Div (numpy-style broadcast), ReduceSum, Log, Scale, ReplaceNaN, MatMul, LeakyRelu, Clip, ConstantFill,
 Shape/Cast (host), AveragedLoss, Accuracy, StopGradient, Concat/Split (views).
 
 Tensors are NCHW / row-major like the reference blobs.  There is no CPU fallback: CPU
@@ -39,6 +39,11 @@ NawsError = _L.NawsError
 def RoIPoolF(X, R, pooled_h=1, pooled_w=1, spatial_scale=1.0, sampling_ratio=0):
     """-> (Y [n,C,ph,pw], argmax int32).  sampling_ratio is ignored (detector.py:321-329)."""
     return _k.roi_pool_f(X, R, pooled_h, pooled_w, spatial_scale, layout='NCHW', with_argmax=True)
+
+
+def RoIPoolFGradient(X, R, argmax, dY):
+    """-> dX (X's shape): dX[b, c, argmax] += dY[r, c, ph, pw]; empty bins (argmax -1) add nothing."""
+    return _k.roi_pool_f_grad(dY.contiguous(), argmax, R, tuple(X.shape), layout='NCHW')
 
 
 def RoIContext(R, X, context_ratio=1.8):
@@ -378,6 +383,23 @@ def Conv(X, W, b, kernel=3, pad=1, stride=1, dilation=1, relu=False):
     return _k.nhwc_to_nchw(y)
 
 
+def ConvGradient(X, W, dY, kernel=3, pad=1, stride=1, dilation=1, need_dx=True):
+    """-> dW (OIHW), db, dX of Conv.  dX is the same convolution of dY with the flipped, transposed
+    weight; dW is nine tap GEMMs on the fp32 MFMA (naws_conv3x3_nhwc_wgrad).  need_dx False: dX is
+    None (behind StopGradient nothing reads it).  conv1_1 (3 input channels) has no weight-gradient
+    form: NawsError UNSUPPORTED, as any channel count that is not a multiple of 32."""
+    if kernel != 3 or stride != 1 or pad != dilation:
+        raise NawsError('ConvGradient', _L.ERR_UNSUPPORTED)
+    x = _k.nchw_to_nhwc(X)
+    dy = _k.nchw_to_nhwc(dY.contiguous())
+    dW, db = _k.conv3x3_nhwc_wgrad(x, dy, dilation)
+    dX = None
+    if need_dx:
+        dX = _k.nhwc_to_nchw(_k.conv3x3_nhwc(dy, _k.conv3x3_dgrad_pack_weight(W), None, dilation,
+                                             relu=False))
+    return dW, db, dX
+
+
 def Relu(X, out=None):
     return _k.unary(_L.UN_RELU, X, out=out)
 
@@ -392,6 +414,14 @@ def MaxPool(X, kernel=2, pad=0, stride=2):
     if kernel != 2 or pad != 0:
         raise NawsError('MaxPool', _L.ERR_UNSUPPORTED)
     return _k.nhwc_to_nchw(_k.maxpool2x2_nhwc(_k.nchw_to_nhwc(X), stride))
+
+
+def MaxPoolGradient(X, Y, dY, kernel=2, pad=0, stride=2):
+    """-> dX: every window's gradient goes to the element the forward kernel selected."""
+    if kernel != 2 or pad != 0:
+        raise NawsError('MaxPoolGradient', _L.ERR_UNSUPPORTED)
+    return _k.nhwc_to_nchw(_k.maxpool2x2_nhwc_grad(_k.nchw_to_nhwc(X), _k.nchw_to_nhwc(Y),
+                                                   _k.nchw_to_nhwc(dY.contiguous()), stride))
 
 
 def _pad_rows4(t):

@@ -37,6 +37,10 @@ PROTOTYPES = {
     'naws_conv3x3_pack_weight': [p, i32, i32, p, p],
     'naws_conv3x3_nhwc_fwd': [p, p, p, i32, i32, i32, i32, i32, i32, i32, p, p],
     'naws_maxpool2x2_nhwc_fwd': [p, i32, i32, i32, i32, i32, p, p],
+    'naws_maxpool2x2_nhwc_bwd': [p, p, p, i32, i32, i32, i32, i32, p, p],
+    'naws_conv3x3_dgrad_pack_weight': [p, i32, i32, p, p],
+    'naws_conv3x3_nhwc_wgrad': [p, p, i32, i32, i32, i32, i32, i32, p, p, p, p],
+    'naws_roi_pool_f_bwd': [p, p, p, i32, i32, i32, i32, i32, i32, i32, i32, p, p],
     'naws_winograd_weight_transform': [p, i32, i32, p, p],
     'naws_conv3x3_winograd_nhwc_fwd': [p, p, p, i32, i32, i32, i32, i32, i32, i32, p, p, p],
     'naws_nchw_to_nhwc': [p, i32, i32, i32, i32, p, p],
@@ -160,6 +164,7 @@ SPECIAL = {
     'naws_winograd_f16x2_workspace_floats': ([i32, i32, i32, i32, i32, i32], i64),
     'naws_winograd4_f16x2_workspace_floats': ([i32, i32, i32, i32, i32, i32], i64),
     'naws_gemm_f32_splitk_workspace_floats': ([i32, i32, i32, i32], i64),
+    'naws_conv3x3_nhwc_wgrad_workspace_floats': ([i32, i32, i32, i32, i32, i32], i64),
 }
 ALL_SYMBOLS = sorted(list(PROTOTYPES) + list(SPECIAL))
 # entries that exist only in the A/B build (make AB=1, loaded through NAWS_LIB): experiments whose

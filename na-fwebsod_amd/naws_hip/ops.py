@@ -118,6 +118,52 @@ def nhwc_to_nchw(x):
     return y
 
 
+# conv body backward (TRAIN.FREEZE_CONV_BODY False on the op-by-op plan)
+def maxpool2x2_nhwc_grad(x, y, dy, stride):
+    """MaxPoolGradient of maxpool2x2_nhwc: x / y the forward's input / output, dy the gradient of
+    y -> dx (x's shape); gather form, windows added in ascending index (bit-reproducible)."""
+    _chk(x, 'x'); _chk(y, 'y'); _chk(dy, 'dy')
+    n, h, w, c = x.shape
+    ho, wo = (h - 2) // stride + 1, (w - 2) // stride + 1
+    if tuple(y.shape) != (n, ho, wo, c) or dy.shape != y.shape:
+        raise L.NawsError('naws_maxpool2x2_nhwc_bwd', L.ERR_SHAPE)
+    dx = torch.empty_like(x)
+    L.call('naws_maxpool2x2_nhwc_bwd', x.data_ptr(), y.data_ptr(), dy.data_ptr(), n, h, w, c,
+           int(stride), dx.data_ptr(), _stream())
+    return dx
+
+
+def conv3x3_dgrad_pack_weight(w_oihw):
+    """OIHW [Cout,Cin,3,3] -> the packed operand [Cin,3,3,Cout] of conv3x3_nhwc for the data
+    gradient: dX = conv3x3_nhwc(dY, this, None, dilation, relu=False)."""
+    _chk(w_oihw, 'w')
+    cout, cin = w_oihw.shape[:2]
+    wp = torch.empty((cin, 3, 3, cout), device=w_oihw.device, dtype=_f32)
+    L.call('naws_conv3x3_dgrad_pack_weight', w_oihw.data_ptr(), cout, cin, wp.data_ptr(),
+           _stream())
+    return wp
+
+
+def conv3x3_nhwc_wgrad(x, dy, dilation=1, workspace=None):
+    """x [N,H,W,Cin], dy [N,H,W,Cout] (NHWC) -> (dW [Cout,Cin,3,3] OIHW, db [Cout]) of the 3x3,
+    stride-1, pad == dilation convolution: padded staging + nine split-K tap GEMMs + one repack."""
+    _chk(x, 'x'); _chk(dy, 'dy')
+    n, h, w, cin = x.shape
+    cout = dy.shape[3]
+    if tuple(dy.shape[:3]) != (n, h, w):
+        raise L.NawsError('naws_conv3x3_nhwc_wgrad', L.ERR_SHAPE)
+    need = L.load().naws_conv3x3_nhwc_wgrad_workspace_floats(n, h, w, cin, cout, int(dilation))
+    if workspace is None:
+        workspace = torch.empty((max(need, 4),), device=x.device, dtype=_f32)
+    if workspace.dtype != _f32 or workspace.numel() < need or not workspace.is_contiguous():
+        raise TypeError('workspace: contiguous fp32, >= naws_conv3x3_nhwc_wgrad_workspace_floats')
+    dw = torch.empty((cout, cin, 3, 3), device=x.device, dtype=_f32)
+    db = torch.empty((cout,), device=x.device, dtype=_f32)
+    L.call('naws_conv3x3_nhwc_wgrad', x.data_ptr(), dy.data_ptr(), n, h, w, cin, cout,
+           int(dilation), workspace.data_ptr(), dw.data_ptr(), db.data_ptr(), _stream())
+    return dw, db
+
+
 # ----------------------------------------------------------------------------
 # RoI ops
 # ----------------------------------------------------------------------------
@@ -153,6 +199,29 @@ def roi_pool_f(x, rois, pooled_h=7, pooled_w=7, spatial_scale=0.125, boost=None,
     L.call('naws_roi_pool_f_fwd', x.data_ptr(), lay, n, c, h, w, rois.data_ptr(), r, _ptr(boost),
            pooled_h, pooled_w, float(spatial_scale), y.data_ptr(), _ptr(am), _stream())
     return (y, am) if with_argmax else y
+
+
+def roi_pool_f_grad(dy, argmax, rois, x_shape, layout='NCHW'):
+    """RoIPoolFGradient: dy / argmax [R,C,ph,pw] as roi_pool_f(with_argmax=True) made them ->
+    dx of shape x_shape (zero-filled here; float atomic adds, see include/naws.h)."""
+    _chk(dy, 'dy'); _chk(rois, 'rois'); _chk(argmax, 'argmax', torch.int32)
+    if rois.dim() != 2 or rois.shape[1] != 5 or dy.dim() != 4 or argmax.shape != dy.shape or \
+            dy.shape[0] != rois.shape[0]:
+        raise L.NawsError('naws_roi_pool_f_bwd', L.ERR_SHAPE)
+    if layout == 'NCHW':
+        n, c, h, w = x_shape
+        lay = L.LAYOUT_NCHW
+    elif layout == 'NHWC':
+        n, h, w, c = x_shape
+        lay = L.LAYOUT_NHWC
+    else:
+        raise L.NawsError('naws_roi_pool_f_bwd', L.ERR_ARG)
+    if dy.shape[1] != c:
+        raise L.NawsError('naws_roi_pool_f_bwd', L.ERR_SHAPE)
+    dx = torch.empty(tuple(x_shape), device=dy.device, dtype=_f32)
+    L.call('naws_roi_pool_f_bwd', dy.data_ptr(), argmax.data_ptr(), rois.data_ptr(),
+           rois.shape[0], lay, n, c, h, w, dy.shape[2], dy.shape[3], dx.data_ptr(), _stream())
+    return dx
 
 
 def roi_context(rois, max_h, max_w, ratio=1.8):

@@ -24,6 +24,7 @@ Blob names, shapes and update rule follow the reference:
 """
 
 import collections
+import contextlib
 import os
 
 import numpy as np
@@ -31,6 +32,7 @@ import torch
 
 from . import lib as L
 from . import ops
+from .planes import ALL, FcPlanes
 from .reducer import ArenaReducer, message_plan, message_slice, owner_blocks, owner_pieces
 
 VGG16_CONVS = [
@@ -118,6 +120,10 @@ ConvLayer = collections.namedtuple('ConvLayer', 'step w b operand direct affine'
 # What a conv chain carries between layers: the activation, the int32 word of an upper bound of
 # max|x| (or None), the (mul, add) to apply to it, and whether the pool that follows is done
 ChainState = collections.namedtuple('ChainState', 'x bound affine pooled')
+# NAWS.PIPELINE_UPDATE: one launch's slice of the arena (seg: the _seg_tables of it; regions None:
+# the element-wise kernel), and an engine's tables (pieces: per FWD_PIECES; ovf: [piece ... | tail])
+UpdatePart = collections.namedtuple('UpdatePart', 'start count seg regions')
+PipeTables = collections.namedtuple('PipeTables', 'pieces bias tail ovf')
 _IDENTITY = (1.0, 0.0)
 
 HIDDEN = 4096
@@ -338,11 +344,8 @@ class WsddnEngine(object):
         self.ROI_POOL_ON_CHAINS = True
         # the 16-bit plans' RoIPoolF reads block-maxima maps of conv5_3, built beside the chains
         self._roi_maps_on_chains = mfma_dtype in ('fp16x2', 'bf16')
-        self._rm_table = None
         self._fc8_ws = None
         self._w6_updated = None      # the region table for the deferred kernel once fc6_w is done
-        self._sgd_regions_rest = None
-        self._sgd_regions = None
         self._seg_ring = None
         self._amax5 = None
         self._streams = []
@@ -352,7 +355,10 @@ class WsddnEngine(object):
         self._upd_event = None
         self._piece_events = None    # pipelined update: [(r0, r1, event)] of the step being joined
         self._pipe = None            # its tables (built on first use)
-        self._wplanes = None         # split planes of fc6_w / fc7_w / fc7_w^T (16-bit MFMA plans)
+        self._pipe_state = None      # its progress while one step's parts are being queued
+        # this step's messages went out in the pipelined order / ... and backward queued the parts
+        self._pipe_sent = self._pipe_eager = self._pipe_warned = False
+        self._fc = None              # FcPlanes: fc6_w / fc7_w / fc7_w^T operand planes (16-bit plans)
         self._planes_dirty = True
         # MEASUREMENT AID: NAWS_ENGINE_SET="DIRECT_MIN_TILES=100000,WINO_F4_MIN_CIN=0" overrides the
         # upper-case integer choices above for every engine of the process (A/B runs of entry points
@@ -389,68 +395,23 @@ class WsddnEngine(object):
         w7 = self.arena.span(self.params, 'fc7_w', '_[noisy]_fc7_w').view(2, HIDDEN, HIDDEN)
         return w6, w7
 
+    # (what tools, tests and bench.py read of the operand planes, under the names they know)
+    _wplanes = property(lambda self: getattr(self._fc, 'operands', None))     # w6 / w7 / w7t
+    _wovf = property(lambda self: getattr(self._fc, 'ovf', None))
+    _rm_table = property(lambda self: getattr(self._fc, 'rm_table', None))
+    _sgd_regions = property(lambda self: getattr(self._fc, 'whole', None))
+    _sgd_regions_rest = property(lambda self: getattr(self._fc, 'rest', None))
+
     def _refresh_weight_planes(self):
         """fp16x2 / fp32x3 / bf16: re-split fc6_w / fc7_w (and fc7_w^T for the dgrad) into their
         16-bit operand planes."""
-        w6, w7 = self._weight_views()
-        cv = {'fp32x3': ops.split_bf16x3, 'fp16x2': ops.split_f16x2}.get(self.mfma_dtype,
-                                                                         ops.to_bf16_slab)
-        if self._wplanes is None and self.mfma_dtype == 'fp16x2':
-            # the scale blocks of w6 / w7 live in one arena, [operand][maxima | 1/scale][8192], so
-            # that the fused SGD kernel can report the updated rows' maxima straight into them
+        if self._fc is None:
             n6 = 2 * HIDDEN
-            self._wscales = torch.zeros((4 * n6,), device=self.device, dtype=torch.float32)
-            f16 = dict(device=self.device, dtype=torch.float16)
-            p6 = ops.F16x2(torch.empty((2, self.k6 // 16, n6, 16), **f16),
-                           self._wscales[:2 * n6].view(2, n6))
-            p7 = ops.F16x2(torch.empty((2, 2, HIDDEN // 16, HIDDEN, 16), **f16),
-                           self._wscales[2 * n6:].view(2, 2, HIDDEN))
-            self._wplanes = dict(w6=cv(w6, out=p6), w7=cv(w7, out=p7), w7t=cv(w7, transpose=True))
-            o6, o7 = self.arena.offsets['fc6_w'][0], self.arena.offsets['fc7_w'][0]
-            self._rm_table = ops.RowmaxTable([(o6, o6 + n6 * self.k6, self.k6, 0),
-                                              (o7, o7 + n6 * HIDDEN, HIDDEN, 2 * n6)], self.device)
-            one_run = (self._one_hyper_run(o6, n6 * self.k6) and self._one_hyper_run(o7, n6 * HIDDEN))
-            if self.k6 % 256 == 0 and one_run:
-                # (a configuration that gives the two branches different lr_mult / weight decay
-                # keeps the element-wise kernel + re-split: _sgd_regions stays None)
-                # [w6 rows | w7 rows]: the maxima before an update (the scale bounds of the planes
-                # the update writes) and the "a row outgrew its bound" word
-                self._wbound = torch.zeros((2 * n6,), device=self.device, dtype=torch.int32)
-                self._wovf = torch.zeros((1,), device=self.device, dtype=torch.int32)
-                sc = self._wscales.view(2, 2, n6)            # [operand][maxima | 1/scale][rows]
-                # fc7_w's COLUMN maxima = the row maxima of fc7_w^T (the dgrad's operand): the
-                # kernel reports them too, so the transposed planes need no maxima pass either
-                cm7 = self._wplanes['w7t'].scales[0].view(torch.int32)
-                self._sgd_regions = ops.SgdPlaneRegions([
-                    (o6, n6, self.k6, n6, p6.planes, self._wbound[:n6], sc[0, 0].view(torch.int32),
-                     sc[0, 1]),
-                    (o7, n6, HIDDEN, HIDDEN, p7.planes, self._wbound[n6:], sc[1, 0].view(torch.int32),
-                     sc[1, 1], cm7)])
-                # the same table with fc6_w marked "updated elsewhere" (train_step)
-                self._sgd_regions_rest = ops.SgdPlaneRegions([
-                    (o6, n6, self.k6, n6, None, None, None, None),
-                    (o7, n6, HIDDEN, HIDDEN, p7.planes, self._wbound[n6:], sc[1, 0].view(torch.int32),
-                     sc[1, 1], cm7)])
-        elif self._wplanes is None:
-            self._wplanes = dict(w6=cv(w6), w7=cv(w7), w7t=cv(w7, transpose=True))
-            n6 = 2 * HIDDEN
-            o6, o7 = self.arena.offsets['fc6_w'][0], self.arena.offsets['fc7_w'][0]
-            if (self.k6 % 256 == 0 and self._one_hyper_run(o6, n6 * self.k6)
-                    and self._one_hyper_run(o7, n6 * HIDDEN)):
-                # fp32x3 / bf16: the SGD kernel writes these planes too (exact / rounded bf16:
-                # no scales, nothing to bound)
-                fmt = L.PLANES_BF16X3 if self.mfma_dtype == 'fp32x3' else L.PLANES_BF16
-                self._sgd_regions = ops.SgdPlaneRegions([
-                    (o6, n6, self.k6, n6, self._wplanes['w6'], None, None, None),
-                    (o7, n6, HIDDEN, HIDDEN, self._wplanes['w7'], None, None, None)], fmt)
-                # the same table with fc6_w marked "updated elsewhere" (train_step, bf16 plan)
-                self._sgd_regions_rest = ops.SgdPlaneRegions([
-                    (o6, n6, self.k6, n6, None, None, None, None),
-                    (o7, n6, HIDDEN, HIDDEN, self._wplanes['w7'], None, None, None)], fmt)
-        else:
-            cv(w6, out=self._wplanes['w6'])
-            cv(w7, out=self._wplanes['w7'])
-            cv(w7, transpose=True, out=self._wplanes['w7t'])
+            o6, ob, o7 = (self.arena.offsets[k][0] for k in ('fc6_w', 'fc6_b', 'fc7_w'))
+            self._fc = FcPlanes(self.mfma_dtype, n6, self.k6, HIDDEN, o6, ob, o7, self.arena.total,
+                                self.device, self._one_hyper_run(o6, n6 * self.k6),
+                                self._one_hyper_run(o7, n6 * HIDDEN))
+        self._fc.split_all(*self._weight_views())
         self._planes_dirty = False
 
     def grad_blob(self, name):
@@ -754,6 +715,21 @@ class WsddnEngine(object):
     def _seed(self, layer):
         return (self.seed * 0x9E3779B1 + self.step_count * 1000003 + layer * 7919) & ((1 << 62) - 1)
 
+    @contextlib.contextmanager
+    def _timed(self, name, on=True):
+        """bench.py's HIP event lists (timing_events, comm_events, update_events): if the engine
+        carries a list called `name` (and `on`), a pair of timing events recorded on the current
+        stream around the body is appended to it; otherwise nothing is recorded."""
+        evs = getattr(self, name, None) if on else None
+        pair = evs is not None and (torch.cuda.Event(enable_timing=True),
+                                    torch.cuda.Event(enable_timing=True))
+        if pair:
+            pair[0].record()
+        yield
+        if pair:
+            pair[1].record()
+            evs.append(pair)
+
     def _take_roi_maps(self, conv5):
         """The block-maxima maps conv_body() built beside the chains, if `conv5` is the very
         tensor it returned, unmodified (same storage, same version counter); None for any other
@@ -828,62 +804,51 @@ class WsddnEngine(object):
             xp = roi_feat if roi_feat.dtype == torch.bfloat16 else ops.split_bf16x3(roi_feat)
         elif bf:
             xp = roi_feat if slab_x else ops.to_bf16_slab(roi_feat)
-        tev = getattr(self, 'timing_events', None)
-        if tev is not None and pieces is None:   # bench.py: HIP events around the dominant kernel
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if h2 and pieces is not None:
-            # fc6 forward piece by piece: piece (r0, r1) = weight rows / h6 columns r0..r1 of one
-            # branch, launched behind the event of ITS update; same kernel, same K order, same
-            # Dropout counters as the one launch below (naws_gemm_f32_f16x2_nt_cols)
-            self._new_amax_arena(rt, nb)
-            sc6n = self._scales(nb, rt)
-            sc6t = self._scales(nb, HIDDEN) if train else None
-            h6 = torch.empty((rt, nb * HIDDEN), device=self.device, dtype=torch.float32)
-            main = torch.cuda.current_stream(self.device)
-            rowwords = ops.amax_words(sc6n)                       # [nb, Rt]
-            colwords = None if sc6t is None else ops.amax_words(sc6t).view(-1)
-            for r0, r1, ev in pieces['fc6']:
-                main.wait_event(ev)
-                if r0 // HIDDEN != (r1 - 1) // HIDDEN:
-                    raise RuntimeError('a forward piece must lie inside one branch')
-                if tev is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                ops.gemm_f32_f16x2_nt_cols(
-                    xp, self._wplanes['w6'].rows(r0, r1), h6[:, r0:r1], r0, nb * HIDDEN,
-                    epilogue=epi, bias=b6[r0:r1], drop_ratio=self.dropout if drop else 0.0,
-                    seed=self._seed(6), rowmax=rowwords[r0 // HIDDEN], rowmax_seg=HIDDEN,
-                    colmax=None if colwords is None else colwords[r0:r1])
-                if tev is not None:
-                    e1.record()
-                    tev.append((e0, e1))
-            self._finish_pieces(pieces)          # fc7 / fc8 read the rest of the update
-            tev = None
-        elif h2:
-            # the GEMM epilogue reports max|h6| per row of each branch (fc7's operand scale) and,
-            # in training, per column (fc7 wgrad's): no pass over h6 for the maxima
-            self._new_amax_arena(rt, nb)
-            sc6n = self._scales(nb, rt)
-            sc6t = self._scales(nb, HIDDEN) if train else None
-            h6 = ops.gemm_f32_f16x2_nt(xp, self._wplanes['w6'].rows(0, nb * HIDDEN), epilogue=epi,
+        # bench.py: HIP events around the dominant kernel (piece by piece: around each piece)
+        with self._timed('timing_events', on=pieces is None):
+            if h2 and pieces is not None:
+                # fc6 forward piece by piece: piece (r0, r1) = weight rows / h6 columns r0..r1 of one
+                # branch, launched behind the event of ITS update; same kernel, same K order, same
+                # Dropout counters as the one launch below (naws_gemm_f32_f16x2_nt_cols)
+                self._new_amax_arena(rt, nb)
+                sc6n = self._scales(nb, rt)
+                sc6t = self._scales(nb, HIDDEN) if train else None
+                h6 = torch.empty((rt, nb * HIDDEN), device=self.device, dtype=torch.float32)
+                main = torch.cuda.current_stream(self.device)
+                rowwords = ops.amax_words(sc6n)                       # [nb, Rt]
+                colwords = None if sc6t is None else ops.amax_words(sc6t).view(-1)
+                for r0, r1, ev in pieces['fc6']:
+                    main.wait_event(ev)
+                    if r0 // HIDDEN != (r1 - 1) // HIDDEN:
+                        raise RuntimeError('a forward piece must lie inside one branch')
+                    with self._timed('timing_events'):
+                        ops.gemm_f32_f16x2_nt_cols(
+                            xp, self._wplanes['w6'].rows(r0, r1), h6[:, r0:r1], r0, nb * HIDDEN,
+                            epilogue=epi, bias=b6[r0:r1], drop_ratio=self.dropout if drop else 0.0,
+                            seed=self._seed(6), rowmax=rowwords[r0 // HIDDEN], rowmax_seg=HIDDEN,
+                            colmax=None if colwords is None else colwords[r0:r1])
+                self._finish_pieces(pieces)          # fc7 / fc8 read the rest of the update
+            elif h2:
+                # the GEMM epilogue reports max|h6| per row of each branch (fc7's operand scale) and,
+                # in training, per column (fc7 wgrad's): no pass over h6 for the maxima
+                self._new_amax_arena(rt, nb)
+                sc6n = self._scales(nb, rt)
+                sc6t = self._scales(nb, HIDDEN) if train else None
+                h6 = ops.gemm_f32_f16x2_nt(xp, self._wplanes['w6'].rows(0, nb * HIDDEN), epilogue=epi,
+                                           bias=b6, drop_ratio=self.dropout if drop else 0.0,
+                                           seed=self._seed(6), rowmax=ops.amax_words(sc6n),
+                                           rowmax_seg=HIDDEN,
+                                           colmax=None if sc6t is None else ops.amax_words(sc6t))
+            elif x3:
+                h6 = ops.gemm_f32x3_nt(xp, self._wplanes['w6'][:, :, :nb * HIDDEN], epilogue=epi,
                                        bias=b6, drop_ratio=self.dropout if drop else 0.0,
-                                       seed=self._seed(6), rowmax=ops.amax_words(sc6n),
-                                       rowmax_seg=HIDDEN,
-                                       colmax=None if sc6t is None else ops.amax_words(sc6t))
-        elif x3:
-            h6 = ops.gemm_f32x3_nt(xp, self._wplanes['w6'][:, :, :nb * HIDDEN], epilogue=epi,
-                                   bias=b6, drop_ratio=self.dropout if drop else 0.0,
-                                   seed=self._seed(6))
-        elif bf:
-            h6 = ops.gemm_bf16_slab_nt(xp, self._wplanes['w6'][:, :nb * HIDDEN], epilogue=epi, bias=b6,
-                                       drop_ratio=self.dropout if drop else 0.0, seed=self._seed(6))
-        else:
-            h6 = ops.gemm(roi_feat, w6[:nb * HIDDEN], False, True, epilogue=epi, bias=b6,
-                          drop_ratio=self.dropout if drop else 0.0, seed=self._seed(6))
-        if tev is not None:
-            e1.record()
-            tev.append((e0, e1))
+                                       seed=self._seed(6))
+            elif bf:
+                h6 = ops.gemm_bf16_slab_nt(xp, self._wplanes['w6'][:, :nb * HIDDEN], epilogue=epi, bias=b6,
+                                           drop_ratio=self.dropout if drop else 0.0, seed=self._seed(6))
+            else:
+                h6 = ops.gemm(roi_feat, w6[:nb * HIDDEN], False, True, epilogue=epi, bias=b6,
+                              drop_ratio=self.dropout if drop else 0.0, seed=self._seed(6))
         xp = None
         h6v = h6.view(rt, nb, HIDDEN).permute(1, 0, 2)       # [nb, Rt, 4096] strided views
         h7 = torch.empty((rt, nb * HIDDEN), device=self.device, dtype=torch.float32)
@@ -1192,54 +1157,47 @@ class WsddnEngine(object):
     def _can_fuse_wgrad_update(self):
         return (self.fuse_wgrad_update and not self.reducer.active and self.iter_size == 1
                 and self.mfma_dtype in ('fp16x2', 'bf16') and self.fused_planes
-                and self._sgd_regions is not None and self._wplanes is not None
-                and not self._planes_dirty and self.k6 % 256 == 0)
+                and self._pipe_planes_ok() and self.k6 % 256 == 0)
+
+    def _w6_sgd_args(self):
+        """For the update in fc6_w's wgrad epilogue: fc6_w, its momentum, and the kernels' SGD
+        arguments lr .. iter_count; raises unless both branches share one hyper-parameter run."""
+        ends, lr_mult, wd = self._seg_host
+        o6, n6 = self.arena.offsets['fc6_w'][0], 2 * HIDDEN
+        sg = next(i for i, e in enumerate(ends) if e > o6)
+        if ends[sg] < o6 + n6 * self.k6:
+            raise RuntimeError('fc6_w and _[noisy]_fc6_w lie in different hyper-parameter runs')
+        m6 = self.arena.span(self.momentum_buf, 'fc6_w', '_[noisy]_fc6_w').view(n6, self.k6)
+        return self._weight_views()[0], m6, (self.lr, lr_mult[sg], wd[sg], self.momentum, 0,
+                                             self.gpu_num, self.sgd_iter_count)
 
     def _wgrad_update_w6(self, dz6t, x, r0, r1, ncut):
         """fc6_w's rows r0..r1: wgrad GEMM with the SGD update + the rows' operand planes in its
         epilogue (ops.gemm_f32_f16x2_nt_xk_sgd), on the main stream.  First chunk: the rows' maxima
         become the bounds of this update; last chunk: the conditional exact re-split."""
-        n6 = 2 * HIDDEN
-        sc = self._wscales.view(2, 2, n6).view(torch.int32)        # [operand][maxima | 1/scale][rows]
-        maxima, bound = sc[0, 0], self._wbound[:n6]
-        tag = self.sgd_iter_count + 1
+        fc, tag = self._fc, self.sgd_iter_count + 1
+        w6, m6, sgd = self._w6_sgd_args()
         if r0 == 0:
-            bound.copy_(maxima)
-            maxima.zero_()
-        w6 = self.arena.span(self.params, 'fc6_w', '_[noisy]_fc6_w').view(n6, self.k6)
-        m6 = self.arena.span(self.momentum_buf, 'fc6_w', '_[noisy]_fc6_w').view(n6, self.k6)
-        ends, lr_mult, wd = self._seg_host
-        o6 = self.arena.offsets['fc6_w'][0]
-        sg = next(i for i, e in enumerate(ends) if e > o6)
-        assert ends[sg] >= o6 + n6 * self.k6       # one hyper-parameter run over both branches
+            fc.begin(ALL, with7=False)
         for c0, c1 in (((0, ncut), (ncut, self.k6)) if ncut else ((0, self.k6),)):
-            ops.gemm_f32_f16x2_nt_xk_sgd(dz6t.rows(r0, r1), x, w6, m6, self.lr, lr_mult[sg], wd[sg],
-                                         self.momentum, 0, self.gpu_num, self.sgd_iter_count,
-                                         self._wplanes['w6'].planes, bound, maxima,
-                                         self._wscales.view(2, 2, n6)[0, 1], self._wovf, tag,
+            ops.gemm_f32_f16x2_nt_xk_sgd(dz6t.rows(r0, r1), x, w6, m6, *sgd, fc.operands['w6'].planes,
+                                         fc.bound(6), fc.maxima(6), fc.inv_scale(6), fc.ovf, tag,
                                          ncols=(c0, c1), rows=(r0, r1))
-        if r1 == n6:
-            ops.split_f16x2_rows_if(w6, maxima, self._wplanes['w6'], self._wovf, tag)
+        if r1 == 2 * HIDDEN:
+            fc.resplit6(w6, ALL, fc.ovf, tag)
             # the route is decided HERE: the deferred kernel of this step must skip fc6_w whatever
             # the toggles say by the time it runs (the table to use travels with the flag)
-            self._w6_updated = self._sgd_regions_rest
+            self._w6_updated = fc.rest
 
     def _wgrad_update_w6_bf16(self, dz6t, xt, r0, r1):
         """The bf16 plan's form of _wgrad_update_w6: fc6_w's rows r0..r1 updated (parameters,
         momentum, the rounded operand plane) in the epilogue of their weight-gradient GEMM
         (ops.gemm_bf16_slab_nt_sgd); no scales, nothing to bound or re-split."""
-        n6 = 2 * HIDDEN
-        w6 = self.arena.span(self.params, 'fc6_w', '_[noisy]_fc6_w').view(n6, self.k6)
-        m6 = self.arena.span(self.momentum_buf, 'fc6_w', '_[noisy]_fc6_w').view(n6, self.k6)
-        ends, lr_mult, wd = self._seg_host
-        o6 = self.arena.offsets['fc6_w'][0]
-        sg = next(i for i, e in enumerate(ends) if e > o6)
-        assert ends[sg] >= o6 + n6 * self.k6       # one hyper-parameter run over both branches
-        ops.gemm_bf16_slab_nt_sgd(dz6t[:, r0:r1], xt, w6, m6, self.lr, lr_mult[sg], wd[sg],
-                                  self.momentum, 0, self.gpu_num, self.sgd_iter_count,
-                                  self._wplanes['w6'], rows=(r0, r1))
-        if r1 == n6:
-            self._w6_updated = self._sgd_regions_rest
+        w6, m6, sgd = self._w6_sgd_args()
+        ops.gemm_bf16_slab_nt_sgd(dz6t[:, r0:r1], xt, w6, m6, *sgd, self._fc.operands['w6'],
+                                  rows=(r0, r1))
+        if r1 == 2 * HIDDEN:
+            self._w6_updated = self._fc.rest
 
     def train_step(self, data, rois, obn_scores, labels_oh, seg=None):
         """forward_backward + sgd_step as one call.  With no gradient exchange between the two
@@ -1291,7 +1249,7 @@ class WsddnEngine(object):
         for the gradient all-reduce and runs the (HBM-bound) fused SGD kernel while the main
         stream already runs the next iteration's (MFMA-bound, parameter-free) conv body + RoIPool;
         `flush()` — called before the head touches the parameters — joins the two streams."""
-        if getattr(self, '_pipe_eager', False):
+        if self._pipe_eager:
             self._pipe_eager = False      # train_step: backward has queued the update already
             return
         defer = True if self.defer_update is None else self.defer_update
@@ -1357,7 +1315,7 @@ class WsddnEngine(object):
                   and self.mfma_dtype == 'fp16x2'
                   and not self.sharded_update and self.iter_size == 1 and self.k6 % 256 == 0
                   and self.fused_planes and (self.defer_update is None or self.defer_update))
-        if on and not getattr(self, '_pipe_warned', False):
+        if on and not self._pipe_warned:
             self._pipe_warned = True
             if self.pg is not None and self.world_size > 1:
                 import torch.distributed as dist
@@ -1378,25 +1336,16 @@ class WsddnEngine(object):
     def _apply_update(self):
         if self._pipe_ready():
             return self._apply_update_pipelined()      # (waits message by message itself)
-        cev = getattr(self, 'comm_events', None)   # bench.py: how long this stream, with this
-        if cev is not None and self.reducer.active:  # rank's gradients complete, waits for the exchange
-            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            c0.record()
-            self.wait_allreduce()
-            c1.record()
-            cev.append((c0, c1))
-        else:
+        # bench.py: how long this stream, with this rank's gradients complete, waits for the exchange
+        with self._timed('comm_events', on=self.reducer.active):
             self.wait_allreduce()
         if self._shard_blocks() is not None:
             return self._apply_update_sharded()
-        uev = getattr(self, 'update_events', None)   # bench.py: HIP events on the update stream
-        if uev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        fc = self._fc
         # fp16x2: the SGD kernel reports max|w| of every updated fc6_w / fc7_w row into the scale
         # blocks of their operand planes, so the re-split reads the weights once (k6 % 256: a
         # wave's 256 floats stay in one row)
-        fused = (self.mfma_dtype == 'fp16x2' and self._wplanes is not None
+        fused = (self.mfma_dtype == 'fp16x2' and fc is not None
                  and self.iter_size == 1 and self.k6 % 256 == 0)
         # (planes marked dirty - a caller wrote through blob() - carry stale maxima: that update
         # takes the exact route below)
@@ -1405,15 +1354,14 @@ class WsddnEngine(object):
         # fp32x3 / bf16: the same kernel with their plane formats (no maxima involved)
         planes_bf = (self.mfma_dtype in ('fp32x3', 'bf16') and self.fused_planes
                      and self._sgd_regions is not None and self.iter_size == 1
-                     and not self._planes_dirty and self._wplanes is not None)
-        rowmax = None
+                     and not self._planes_dirty and fc is not None)
         rest, self._w6_updated = self._w6_updated, None
         w6_done = rest is not None
         if w6_done:
             # fc6_w (weights, momentum, planes) was updated by its wgrad GEMM in this step's
             # backward: the rest MUST take the plane-writing kernel with fc6_w's region skipped,
             # even if an A/B tool has flipped fused_planes since
-            if (self._wplanes is None or self._sgd_regions is None
+            if (fc is None or self._sgd_regions is None
                     or self.mfma_dtype not in ('fp16x2', 'bf16')):
                 raise RuntimeError('fc6_w was updated in its wgrad epilogue but the plane state '
                                    'it belongs to is gone (engine toggles changed mid-step?)')
@@ -1421,62 +1369,45 @@ class WsddnEngine(object):
                 planes_bf = True
             else:
                 fused = planes = True
-        if fused:
-            maxima = self._wscales.view(2, 2, 2 * HIDDEN)[:, 0]
-            part = slice(1, 2) if w6_done else slice(0, 2)      # (fc6_w's half was handled by its wgrad)
+        regions = rest if w6_done else self._sgd_regions
+        w6, w7 = self._weight_views()
+        tag = self.sgd_iter_count + 1
+        with self._timed('update_events'):          # bench.py: HIP events on the update stream
             if planes:
-                self._wbound.view(2, 2 * HIDDEN)[part].copy_(maxima.view(torch.int32)[part])
-            maxima[part].zero_()
-            rowmax = self._wscales.view(torch.int32)
-        if planes:
-            tag = self.sgd_iter_count + 1
-            self._wplanes['w7t'].scales[0].zero_()
-            ops.acm_sgd_update_f16x2(self.grads, self.momentum_buf, self.lr, self.params,
-                                     self.seg_end, self.seg_lr_mult, self.seg_wd, self.momentum, 0,
-                                     self.gpu_num, self.sgd_iter_count,
-                                     rest if w6_done else self._sgd_regions,
-                                     self._wovf, tag)
-        elif planes_bf:
-            ops.acm_sgd_update_planes(self.grads, self.momentum_buf, self.lr, self.params,
-                                      self.seg_end, self.seg_lr_mult, self.seg_wd, self.momentum, 0,
-                                      self.gpu_num, self.sgd_iter_count,
-                                      rest if w6_done else self._sgd_regions)
-        else:
-            ops.acm_sgd_update(self.grads, self.momentum_buf, self.lr, self.params, self.acmgrad,
-                               self.seg_end, self.seg_lr_mult, self.seg_wd, self.momentum, 0,
-                               self.iter_size, self.gpu_num, self.sgd_iter_count, rowmax=rowmax,
-                               rm_table=self._rm_table if fused else None)
-        if uev is not None:
-            e1.record()
-            uev.append((e0, e1))
+                fc.begin(None if w6_done else ALL, with7=True)     # (fc6_w's half: its wgrad's)
+                self._sgd_f16x2(regions, fc.ovf, tag)
+            elif planes_bf:
+                ops.acm_sgd_update_planes(self.grads, self.momentum_buf, self.lr, self.params,
+                                          self.seg_end, self.seg_lr_mult, self.seg_wd, self.momentum, 0,
+                                          self.gpu_num, self.sgd_iter_count, regions)
+            else:
+                ops.acm_sgd_update(self.grads, self.momentum_buf, self.lr, self.params, self.acmgrad,
+                                   self.seg_end, self.seg_lr_mult, self.seg_wd, self.momentum, 0,
+                                   self.iter_size, self.gpu_num, self.sgd_iter_count,
+                                   rowmax=fc.zeroed_rowmax() if fused else None,
+                                   rm_table=self._rm_table if fused else None)
         self.sgd_iter_count += 1
         if planes:
-            # the planes are written; should a row have outgrown twice its old maximum, these two
-            # launches redo them from the exact maxima (otherwise their workgroups leave at once)
-            w6, w7 = self._weight_views()
-            wp = self._wplanes
-            sc = self._wscales.view(2, 2, 2 * HIDDEN).view(torch.int32)
             if not w6_done:
-                ops.split_f16x2_rows_if(w6, sc[0, 0], wp['w6'], self._wovf, tag)
-            ops.split_f16x2_rows_if(w7, sc[1, 0], wp['w7'], self._wovf, tag)
-            # fc7_w^T from the column maxima the SGD kernel has just reported: one pass
-            # (was: a maxima pass + a transposing split, 92 + 116 us)
-            ops.split_f16x2_dual(w7, None, wp['w7t'].scales, out_t=wp['w7t'])
-            self._planes_dirty = False
+                fc.resplit6(w6, ALL, fc.ovf, tag)
+            fc.finish7(w7, fc.ovf, tag)
         elif fused:                            # same stream as the update: hidden with it
-            w6, w7 = self._weight_views()
-            wp = self._wplanes
-            q6 = ops.split_f16x2_dual(w6, wp['w6'].scales, None, out_n=wp['w6'])[0]
-            q7 = ops.split_f16x2_dual(w7, wp['w7'].scales, None, out_n=wp['w7'])[0]
-            assert q6 is wp['w6'] and q7 is wp['w7']
-            ops.split_f16x2(w7, transpose=True, out=wp['w7t'])
-            self._planes_dirty = False
+            fc.split_from_maxima(w6, w7)
         elif planes_bf:
-            cv = ops.split_bf16x3 if self.mfma_dtype == 'fp32x3' else ops.to_bf16_slab
-            cv(self._weight_views()[1], transpose=True, out=self._wplanes['w7t'])
+            fc.convert(w7, transpose=True, out=fc.operands['w7t'])
+        elif fc is not None:
+            fc.split_all(w6, w7)
+        if fc is not None:
             self._planes_dirty = False
-        elif self.mfma_dtype != 'fp32' and self._wplanes is not None:
-            self._refresh_weight_planes()
+
+    def _sgd_f16x2(self, regions, ovf, tag, part=None):
+        """The plane-writing SGD kernel (fp16x2) over the whole arena, or over `part` (an
+        UpdatePart) of it; `ovf` receives `tag` when a row outgrew its bound."""
+        a, b = (0, self.arena.total) if part is None else (part.start, part.start + part.count)
+        seg = (self.seg_end, self.seg_lr_mult, self.seg_wd) if part is None else part.seg
+        ops.acm_sgd_update_f16x2(self.grads[a:b], self.momentum_buf[a:b], self.lr, self.params[a:b],
+                                 *seg, self.momentum, 0, self.gpu_num, self.sgd_iter_count, regions,
+                                 ovf, tag)
 
     # ------------------------------------------------- NAWS.PIPELINE_UPDATE
     FWD_PIECES = ((0, HIDDEN), (HIDDEN, 2 * HIDDEN))      # one branch each: 16 x 16 tiles of 256 x 256
@@ -1487,55 +1418,24 @@ class WsddnEngine(object):
         can run on them (planes valid, one hyper-parameter run per weight matrix); otherwise the
         update waits for everything and takes the one-launch route - any message order is fine
         for that."""
-        return (getattr(self, '_pipe_sent', False) and self._pipe_planes_ok()
+        return (self._pipe_sent and self._pipe_planes_ok()
                 and self._upd_stream is not None
                 and torch.cuda.current_stream(self.device) == self._upd_stream)
 
     def _pipe_planes_ok(self):
-        return (self._wplanes is not None and self._sgd_regions is not None
-                and not self._planes_dirty)
+        return self._sgd_regions is not None and not self._planes_dirty
 
     def _seg_tables(self, start, count):
         """(seg_end, seg_lr_mult, seg_wd) device tensors of the arena range [start, start + count),
         ends relative to `start` (the SGD kernels take a base pointer + per-run hyper-parameters)."""
         ends, lr_mult, wd = self._seg_host
-        e2, l2, w2 = [], [], []
-        for e, l, w in zip(ends, lr_mult, wd):
-            if e <= start:
-                continue
-            e2.append(min(e, start + count) - start)
-            l2.append(l)
-            w2.append(w)
-            if e >= start + count:
-                break
-        return (torch.tensor(e2, dtype=torch.int64, device=self.device),
-                torch.tensor(l2, dtype=torch.float32, device=self.device),
-                torch.tensor(w2, dtype=torch.float32, device=self.device))
-
-    def _pipe_tables(self):
-        if self._pipe is None:
-            n6 = 2 * HIDDEN
-            o6, ob, o7 = (self.arena.offsets[k][0] for k in ('fc6_w', 'fc6_b', 'fc7_w'))
-            sc = self._wscales.view(2, 2, n6)                # [operand][maxima | 1/scale][rows]
-            p6, p7 = self._wplanes['w6'], self._wplanes['w7']
-            cm7 = self._wplanes['w7t'].scales[0].view(torch.int32)
-            pieces = []
-            for r0, r1 in self.FWD_PIECES:
-                regs = ops.SgdPlaneRegions([(0, r1 - r0, self.k6, n6, (p6.planes, r0),
-                                             self._wbound[r0:r1], sc[0, 0].view(torch.int32)[r0:r1],
-                                             sc[0, 1][r0:r1])])
-                pieces.append(dict(rows=(r0, r1), start=o6 + r0 * self.k6, count=(r1 - r0) * self.k6,
-                                   regions=regs, seg=self._seg_tables(o6 + r0 * self.k6,
-                                                                      (r1 - r0) * self.k6)))
-            tail = ops.SgdPlaneRegions([(0, n6, HIDDEN, HIDDEN, p7.planes, self._wbound[n6:],
-                                         sc[1, 0].view(torch.int32), sc[1, 1], cm7)])
-            self._pipe = dict(pieces=pieces, bias=dict(start=ob, count=o7 - ob,
-                                                       seg=self._seg_tables(ob, o7 - ob)),
-                              tail=dict(start=o7, count=self.arena.total - o7, regions=tail,
-                                        seg=self._seg_tables(o7, self.arena.total - o7)),
-                              ovf=torch.zeros((len(self.FWD_PIECES) + 1,), device=self.device,
-                                              dtype=torch.int32))
-        return self._pipe
+        first = next(i for i, e in enumerate(ends) if e > start)          # the runs that overlap it
+        last = next((i for i, e in enumerate(ends) if e >= start + count), len(ends) - 1)
+        runs = slice(first, last + 1)
+        return (torch.tensor([min(e, start + count) - start for e in ends[runs]], dtype=torch.int64,
+                             device=self.device),
+                torch.tensor(lr_mult[runs], dtype=torch.float32, device=self.device),
+                torch.tensor(wd[runs], dtype=torch.float32, device=self.device))
 
     def _apply_update_pipelined(self):
         """The deferred update of an N > 1 step, piece by piece (update stream).  Messages arrive
@@ -1564,20 +1464,24 @@ class WsddnEngine(object):
             self._pipe_enqueue_piece(i)
         self._pipe_enqueue_tail()
 
-    def _pipe_slice(self, flat, t):
-        return flat[t['start']:t['start'] + t['count']]
-
     def _pipe_begin(self):
         """Start of one step's piece-by-piece update (current stream = the update stream)."""
-        self._pipe_tables()
+        if self._pipe is None:
+            def part(start, count, regions):
+                return UpdatePart(start, count, self._seg_tables(start, count), regions)
+            fc = self._fc
+            self._pipe = PipeTables([part(*fc.piece(r0, r1)) for r0, r1 in self.FWD_PIECES],
+                                    part(fc.ob, fc.o7 - fc.ob, None), part(*fc.tail()),
+                                    torch.zeros((len(self.FWD_PIECES) + 1,), device=self.device,
+                                                dtype=torch.int32))
         self._pipe_state = dict(arrived=0, events=[], tag=self.sgd_iter_count + 1, grads_ready=None)
 
     def _pipe_enqueue_bias(self):
-        tb, b = self._pipe, self._pipe['bias']
+        b = self._pipe.bias
+        sl = slice(b.start, b.start + b.count)
         self.reducer.wait_first(1)
-        ops.acm_sgd_update(self._pipe_slice(self.grads, b), self._pipe_slice(self.momentum_buf, b),
-                           self.lr, self._pipe_slice(self.params, b), None, b['seg'][0], b['seg'][1],
-                           b['seg'][2], self.momentum, 0, 1, self.gpu_num, self.sgd_iter_count)
+        ops.acm_sgd_update(self.grads[sl], self.momentum_buf[sl], self.lr, self.params[sl], None,
+                           *b.seg, self.momentum, 0, 1, self.gpu_num, self.sgd_iter_count)
 
     def _pipe_chunks_below(self, row):
         """How many fc6_w messages start below `row` (= must have arrived before rows < row are
@@ -1586,62 +1490,30 @@ class WsddnEngine(object):
                    if kind == 'fc6_w' and rows[0] < row)
 
     def _pipe_enqueue_piece(self, i):
-        n6 = 2 * HIDDEN
-        st, pc = self._pipe_state, self._pipe['pieces'][i]
-        r0, r1 = pc['rows']
-        need = self._pipe_chunks_below(r1)
+        st, fc, rows = self._pipe_state, self._fc, self.FWD_PIECES[i]
+        need = self._pipe_chunks_below(rows[1])
         self.reducer.wait_first(need - st['arrived'])
         st['arrived'] = need
-        sc = self._wscales.view(2, 2, n6)
-        max6 = sc[0, 0].view(torch.int32)
-        self._wbound[r0:r1].copy_(max6[r0:r1])
-        max6[r0:r1].zero_()
-        ovf = self._pipe['ovf'][i:i + 1]
-        w6, _w7 = self._weight_views()
-        ops.acm_sgd_update_f16x2(self._pipe_slice(self.grads, pc), self._pipe_slice(self.momentum_buf, pc),
-                                 self.lr, self._pipe_slice(self.params, pc), pc['seg'][0], pc['seg'][1],
-                                 pc['seg'][2], self.momentum, 0, self.gpu_num, self.sgd_iter_count,
-                                 pc['regions'], ovf, st['tag'])
-        ops.split_f16x2_row_range_if(w6, max6, self._wplanes['w6'], r0, r1, cond=ovf, cond_value=st['tag'])
-        st['events'].append((r0, r1, self._upd_stream.record_event()))
+        ovf = self._pipe.ovf[i:i + 1]
+        fc.begin(rows, with7=False)
+        self._sgd_f16x2(self._pipe.pieces[i].regions, ovf, st['tag'], self._pipe.pieces[i])
+        fc.resplit6(self._weight_views()[0], rows, ovf, st['tag'])
+        st['events'].append((rows[0], rows[1], self._upd_stream.record_event()))
 
     def _pipe_enqueue_tail(self):
-        n6 = 2 * HIDDEN
-        st, t, wp = self._pipe_state, self._pipe['tail'], self._wplanes
+        st, fc, t = self._pipe_state, self._fc, self._pipe.tail
         # bench.py (comm_events): how long this stream, with this rank's gradients complete, still
-        # waits for the exchange (queued from inside backward: `grads_ready` = the main stream's
-        # position behind the last gradient kernel)
-        cev = getattr(self, 'comm_events', None)
-        if cev is not None:
-            if st['grads_ready'] is not None:
-                self._upd_stream.wait_event(st['grads_ready'])
-            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            c0.record()
-        self.reducer.wait()
-        if cev is not None:
-            c1.record()
-            cev.append((c0, c1))
-        uev = getattr(self, 'update_events', None)
-        if uev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        sc = self._wscales.view(2, 2, n6)
-        max7 = sc[1, 0].view(torch.int32)
-        self._wbound[n6:].copy_(max7)
-        max7.zero_()
-        wp['w7t'].scales[0].zero_()
-        ovf = self._pipe['ovf'][-1:]
-        _w6, w7 = self._weight_views()
-        ops.acm_sgd_update_f16x2(self._pipe_slice(self.grads, t), self._pipe_slice(self.momentum_buf, t),
-                                 self.lr, self._pipe_slice(self.params, t), t['seg'][0], t['seg'][1],
-                                 t['seg'][2], self.momentum, 0, self.gpu_num, self.sgd_iter_count,
-                                 t['regions'], ovf, st['tag'])
-        if uev is not None:
-            e1.record()
-            uev.append((e0, e1))
+        # waits for the exchange (`grads_ready`: the main stream behind the last gradient kernel)
+        if getattr(self, 'comm_events', None) is not None and st['grads_ready'] is not None:
+            self._upd_stream.wait_event(st['grads_ready'])
+        with self._timed('comm_events'):
+            self.reducer.wait()
+        ovf = self._pipe.ovf[-1:]
+        with self._timed('update_events'):
+            fc.begin(None, with7=True)
+            self._sgd_f16x2(t.regions, ovf, st['tag'], t)
         self.sgd_iter_count += 1
-        ops.split_f16x2_rows_if(w7, max7, wp['w7'], ovf, st['tag'])
-        ops.split_f16x2_dual(w7, None, wp['w7t'].scales, out_t=wp['w7t'])
+        fc.finish7(self._weight_views()[1], ovf, st['tag'])
         self._planes_dirty = False
         self._piece_events = dict(fc6=st['events'], done=self._upd_stream.record_event())
         self._pipe_state = None
@@ -1673,35 +1545,6 @@ class WsddnEngine(object):
                                   'all-reduce route' % dist.get_backend(self.pg))
         return self._shard['blocks']
 
-    def _shard_tables(self):
-        sh = self._shard
-        if 'regions' not in sh:
-            if self._wplanes is None or self._sgd_regions is None:
-                raise RuntimeError('the sharded update needs the plane-writing SGD kernel '
-                                   '(one hyper-parameter run over fc6_w / fc7_w)')
-            n6 = 2 * HIDDEN
-            b0, b1 = sh['blocks'][self.rank]
-            nb = b1 - b0
-            o6, o7 = self.arena.offsets['fc6_w'][0], self.arena.offsets['fc7_w'][0]
-            sc = self._wscales.view(2, 2, n6)                # [operand][maxima | 1/scale][rows]
-            p6, p7 = self._wplanes['w6'], self._wplanes['w7']
-            cm7 = self._wplanes['w7t'].scales[0].view(torch.int32)
-            regs = []
-            if b0 > 0:
-                regs.append((o6, b0, self.k6, 32, None, None, None, None))
-            regs.append((o6 + b0 * self.k6, nb, self.k6, n6,
-                         p6.planes if nb == n6 else (p6.planes, b0), self._wbound[b0:b1],
-                         sc[0, 0].view(torch.int32)[b0:b1], sc[0, 1][b0:b1]))
-            if b1 < n6:
-                regs.append((o6 + b1 * self.k6, n6 - b1, self.k6, 32, None, None, None, None))
-            regs.append((o7, n6, HIDDEN, HIDDEN, p7.planes, self._wbound[n6:],
-                         sc[1, 0].view(torch.int32), sc[1, 1], cm7))
-            sh['regions'] = ops.SgdPlaneRegions(regs)
-            # what travels back beside the fp32 rows: per owner [row maxima | 1/scale | overflow word]
-            sh['meta'] = torch.zeros((len(sh['blocks']), 2 * nb + 4), device=self.device,
-                                     dtype=torch.int32)
-        return sh['regions'], sh['meta']
-
     def _apply_update_sharded(self):
         """The deferred update of a rank under NAWS.SHARDED_UPDATE (update stream):
           1. wait for the reduces of this rank's fc6_w rows and for the small all-reduce;
@@ -1713,43 +1556,36 @@ class WsddnEngine(object):
              the owners' bound-derived ones, or - if ANY row of any owner outgrew its bound, which
              is what the single overflow word of the all-reduce route records - the exact maxima.
         fc7_w / fc8 / biases: as in the all-reduce route (every rank updates them)."""
-        n6 = 2 * HIDDEN
-        blocks = self._shard['blocks']
+        blocks, red, fc, n6 = self._shard['blocks'], self.reducer, self._fc, 2 * HIDDEN
         b0, b1 = blocks[self.rank]
         nb = b1 - b0
-        red = self.reducer
         self.wait_allreduce()
-        if self._planes_dirty or self._wplanes is None:
+        if self._planes_dirty or fc is None:
             raise RuntimeError('sharded update: the operand planes are stale (blob() written '
                                'through between backward and update?)')
-        regions, meta = self._shard_tables()
-        sc = self._wscales.view(2, 2, n6)
-        max6, max7 = sc[0, 0].view(torch.int32), sc[1, 0].view(torch.int32)
+        sh = self._shard
+        if 'regions' not in sh:
+            if self._sgd_regions is None:
+                raise RuntimeError('the sharded update needs the plane-writing SGD kernel '
+                                   '(one hyper-parameter run over fc6_w / fc7_w)')
+            sh['regions'] = fc.shard_table(b0, b1)
+            # what travels back beside the fp32 rows: per owner [row maxima | 1/scale | overflow word]
+            sh['meta'] = torch.zeros((len(blocks), 2 * nb + 4), device=self.device, dtype=torch.int32)
+        regions, meta = sh['regions'], sh['meta']
+        max6 = fc.maxima(6)
         tag = self.sgd_iter_count + 1
-        self._wbound[b0:b1].copy_(max6[b0:b1])
-        max6[b0:b1].zero_()
-        self._wbound[n6:].copy_(max7)
-        max7.zero_()
-        self._wplanes['w7t'].scales[0].zero_()
-        uev = getattr(self, 'update_events', None)
-        if uev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        ops.acm_sgd_update_f16x2(self.grads, self.momentum_buf, self.lr, self.params, self.seg_end,
-                                 self.seg_lr_mult, self.seg_wd, self.momentum, 0, self.gpu_num,
-                                 self.sgd_iter_count, regions, self._wovf, tag)
-        if uev is not None:
-            e1.record()
-            uev.append((e0, e1))
+        fc.begin((b0, b1), with7=True)
+        with self._timed('update_events'):
+            self._sgd_f16x2(regions, fc.ovf, tag)
         self.sgd_iter_count += 1
         self._mom_synced = len(blocks) == 1
         # every owner's block starts from this rank's own view of those rows (what the previous
         # gather left: right for the rows this rank does not own only until the gather below
         # overwrites them - and what an exchange that moves no data, bench.py's projection, keeps)
         meta[:, :nb].copy_(max6.view(len(blocks), nb))
-        meta[:, nb:2 * nb].copy_(sc[0, 1].view(torch.int32).view(len(blocks), nb))
+        meta[:, nb:2 * nb].copy_(fc.inv_scale(6).view(torch.int32).view(len(blocks), nb))
         meta[:, 2 * nb].zero_()
-        meta[self.rank, 2 * nb:2 * nb + 1].copy_(self._wovf)
+        meta[self.rank, 2 * nb:2 * nb + 1].copy_(fc.ovf)
         w6, w7 = self._weight_views()
         red.gather_blocks_async(w6.reshape(-1), self.rank)
         red.gather_blocks_async(meta.view(-1), self.rank)
@@ -1759,19 +1595,17 @@ class WsddnEngine(object):
         bound_scale = (meta[:, nb:2 * nb].reshape(n6).view(torch.float32) * 16384.0).view(torch.int32)
         max6.copy_(rowmax)
         eff = torch.where(raised, rowmax, bound_scale)     # 1/scale = 2^(e-14)  ->  a maximum 2^e
-        self._wovf.copy_(torch.where(raised, torch.full_like(self._wovf, tag), self._wovf))
-        wp = self._wplanes
+        fc.ovf.copy_(torch.where(raised, torch.full_like(fc.ovf, tag), fc.ovf))
         # the rows this rank does NOT own: planes from the owners' scales (always); its own rows
         # already carry the planes its SGD kernel wrote with exactly those scales - they are redone
         # (from the exact maxima) only if some owner raised the overflow word (the full
         # re-split gave back most of what the owner-only update saves)
         if b0 > 0:
-            ops.split_f16x2_row_range_if(w6, eff, wp['w6'], 0, b0)
+            fc.resplit6(w6, (0, b0), rowmax=eff)
         if b1 < n6:
-            ops.split_f16x2_row_range_if(w6, eff, wp['w6'], b1, n6)
-        ops.split_f16x2_row_range_if(w6, eff, wp['w6'], b0, b1, cond=self._wovf, cond_value=tag)
-        ops.split_f16x2_rows_if(w7, max7, wp['w7'], self._wovf, tag)
-        ops.split_f16x2_dual(w7, None, wp['w7t'].scales, out_t=wp['w7t'])
+            fc.resplit6(w6, (b1, n6), rowmax=eff)
+        fc.resplit6(w6, (b0, b1), fc.ovf, tag, rowmax=eff)
+        fc.finish7(w7, fc.ovf, tag)
         self._planes_dirty = False
 
     def gather_sharded_state(self):

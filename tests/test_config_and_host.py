@@ -733,3 +733,115 @@ def test_whole_minibatch_matches_the_reference_capture(tag, over, raw, monkeypat
                 for r in blobs['_raw']] == frm.tolist()
     else:
         assert list(blobs['data'].shape) == g[tag + '__data_shape'].tolist()
+
+
+# ---- the fc operand planes' owner: layout of the scale arena, every SGD region table ------------
+
+def test_fc_planes_layout_and_region_tables(monkeypatch):
+    """naws_hip.planes.FcPlanes on the CPU at rows6 = 256 (two branches of 128), k6 = 256, hidden =
+    128: every region table the update routes launch with (whole, fc6_w done elsewhere, pipelined
+    pieces and tail, the owners' shard tables) entry by entry, the named views' places in the one
+    scale arena, the cases that have no table, the fp32x3 / bf16 tables - and the engine's timing
+    helper with no event list set."""
+    import torch
+    from naws_hip.engine import WsddnEngine
+    from naws_hip.planes import FcPlanes
+    from naws_hip.reducer import owner_blocks
+    n6, k6, hid = 256, 256, 128
+    o6, total = 1024, 200000
+    ob = o6 + n6 * k6
+    o7 = ob + n6
+    cpu = torch.device('cpu')
+    fc = FcPlanes('fp16x2', n6, k6, hid, o6, ob, o7, total, cpu)
+    p6, p7, p7t = (fc.operands[k] for k in ('w6', 'w7', 'w7t'))
+
+    def check(table, origin, own, skips, with7):
+        """own: (r0, r1) or None; skips: [(r0, r1, rows_per_batch)]; entries ascending."""
+        want = sorted([(r0, r1, rpb, False) for r0, r1, rpb in skips]
+                      + ([(own[0], own[1], n6, True)] if own else []))
+        assert table.n == len(want) + int(with7)
+        for h, (r0, r1, rpb, owned) in zip(table.host, want):
+            assert (h.start, h.rows, h.cols, h.rows_per_batch) == (o6 + r0 * k6 - origin, r1 - r0, k6, rpb)
+            assert not h.colmax
+            if not owned:
+                assert not h.planes and not (h.bound or h.rowmax or h.inv_scale)
+                continue
+            assert h.planes - p6.planes.data_ptr() == r0 * 16 * 2
+            assert h.plane_stride == p6.planes.stride(0)
+            assert h.bound == fc.bound(6, (r0, r1)).data_ptr() == fc.bound(6).data_ptr() + 4 * r0
+            assert h.rowmax == fc.maxima(6, (r0, r1)).data_ptr() == fc.maxima(6).data_ptr() + 4 * r0
+            assert h.inv_scale == fc.inv_scale(6, (r0, r1)).data_ptr() == fc.inv_scale(6).data_ptr() + 4 * r0
+        if with7:
+            h = table.host[table.n - 1]
+            assert (h.start, h.rows, h.cols, h.rows_per_batch) == (o7 - origin, n6, hid, hid)
+            assert h.planes == p7.planes.data_ptr() and h.plane_stride == p7.planes.stride(0)
+            assert (h.bound, h.rowmax, h.inv_scale, h.colmax) == (
+                fc.bound(7).data_ptr(), fc.maxima(7).data_ptr(), fc.inv_scale(7).data_ptr(),
+                fc.colmax7.data_ptr())
+
+    check(fc.whole, 0, (0, n6), [], True)
+    check(fc.rest, 0, None, [(0, n6, n6)], True)
+    for r0, r1 in ((0, 128), (128, 256)):
+        start, count, table = fc.piece(r0, r1)
+        assert (start, count) == (o6 + r0 * k6, (r1 - r0) * k6)
+        check(table, start, (r0, r1), [], False)
+    start, count, table = fc.tail()
+    assert (start, count) == (o7, total - o7)
+    check(table, o7, None, [], True)
+    assert (fc.ob, fc.o7) == (ob, o7)
+    for rank, world in ((0, 1), (0, 2), (1, 2), (1, 4)):
+        b0, b1 = owner_blocks(n6, world)[rank]
+        skips = [(a, b, 32) for a, b in ((0, b0), (b1, n6)) if a < b]
+        check(fc.shard_table(b0, b1), 0, (b0, b1), skips, True)
+
+    # the one scale arena: [fc6 maxima | fc6 1/scale | fc7 maxima | fc7 1/scale], n6 words each
+    base = fc.scales.data_ptr()
+    assert fc.scales.numel() == 4 * n6 and fc.scales.dtype == torch.float32
+    views = (fc.maxima(6), fc.inv_scale(6), fc.maxima(7), fc.inv_scale(7))
+    assert [v.data_ptr() - base for v in views] == [4 * n6 * i for i in range(4)]
+    assert all(v.numel() == n6 and v.is_contiguous() for v in views)
+    assert [v.dtype for v in views] == [torch.int32, torch.float32, torch.int32, torch.float32]
+    assert p6.scales.data_ptr() == base and tuple(p6.scales.shape) == (2, n6)
+    assert p7.scales.data_ptr() == base + 8 * n6 and tuple(p7.scales.shape) == (2, 2, hid)
+    assert p6.scales._base is fc.scales and p7.scales._base is fc.scales
+    assert p6.inv_scale.data_ptr() == fc.inv_scale(6).data_ptr()
+    assert p7.inv_scale.data_ptr() == fc.inv_scale(7).data_ptr()
+    assert fc.bound(7).data_ptr() == fc.bound(6).data_ptr() + 4 * n6 and fc.bound(7).numel() == n6
+    assert fc.colmax7.data_ptr() == p7t.scales.data_ptr() and fc.colmax7.numel() == n6
+    assert tuple(p6.planes.shape) == (2, k6 // 16, n6, 16)
+    assert tuple(p7.planes.shape) == tuple(p7t.planes.shape) == (2, 2, hid // 16, hid, 16)
+    assert fc.rm_table.host.tolist() == [[o6, o6 + n6 * k6, k6, 0], [o7, o7 + n6 * hid, hid, 2 * n6]]
+
+    # no table: a row that is no multiple of a wave's 256 floats, or two hyper-parameter runs
+    for kw in (dict(k6=250), dict(one_run6=False), dict(one_run7=False)):
+        k = kw.pop('k6', k6)
+        off = FcPlanes('fp16x2', n6, k, hid, o6, o6 + n6 * k, o6 + n6 * k + n6, total, cpu, **kw)
+        assert off.whole is None and off.rest is None and off.ovf is None
+        assert off.rm_table is not None and off.maxima(6).numel() == n6
+
+    # fp32x3 / bf16: two entries, planes only
+    for plan, lead in (('fp32x3', (3,)), ('bf16', ())):
+        f = FcPlanes(plan, n6, k6, hid, o6, ob, o7, total, cpu)
+        assert f.scales is None and f.ovf is None and f.rm_table is None
+        assert tuple(f.operands['w6'].shape) == lead + (k6 // 16, n6, 16)
+        for table, own6 in ((f.whole, True), (f.rest, False)):
+            assert table.n == 2 and table.fmt != fc.whole.fmt
+            h6, h7 = table.host[0], table.host[1]
+            assert (h6.start, h6.rows, h6.cols, h6.rows_per_batch) == (o6, n6, k6, n6)
+            assert (h7.start, h7.rows, h7.cols, h7.rows_per_batch) == (o7, n6, hid, hid)
+            assert h6.planes == (f.operands['w6'].data_ptr() if own6 else None)
+            assert h7.planes == f.operands['w7'].data_ptr()
+            for h in (h6, h7):
+                assert not (h.bound or h.rowmax or h.inv_scale or h.colmax)
+        assert FcPlanes(plan, n6, 250, hid, o6, ob, o7, total, cpu).whole is None
+
+    # the timing helper without its list (absent, or None): the body runs, no event is made
+    made = []
+    monkeypatch.setattr(torch.cuda, 'Event', lambda *a, **k: made.append(1))
+    eng = WsddnEngine.__new__(WsddnEngine)
+    eng.update_events = None
+    ran = []
+    for name, on in (('comm_events', True), ('update_events', True), ('timing_events', False)):
+        with eng._timed(name, on=on):
+            ran.append(name)
+    assert len(ran) == 3 and not made

@@ -30,6 +30,7 @@ import os
 import numpy as np
 import torch
 
+from . import head_arith
 from . import lib as L
 from . import ops
 from .planes import ALL, FcPlanes
@@ -108,10 +109,8 @@ def _conv_operand(form, w):
         m = ops.winograd_weight_transform(w)
     else:
         m = ops.conv3x3_pack_weight(w).view(w.shape[0], -1)
-    if form.startswith('f32'):
-        return m
-    split = {'h2': ops.split_f16x2, 'x3': ops.split_bf16x3, 'bf16': ops.to_bf16_slab}
-    return split[form.split('_')[0]](m)
+    ar = next(a for a in head_arith.PLANS.values() if form.startswith(a.conv_prefix + '_'))
+    return ar.split(m) if ar.planes16 else m
 
 
 # An entry packed by set_conv_blobs: the step and, for a conv, the fp32 weight and bias, its form's
@@ -198,22 +197,8 @@ class WsddnEngine(object):
         if not freeze_conv_body:
             raise NotImplementedError('only TRAIN.FREEZE_CONV_BODY: True is on the hot path '
                                       '(SURVEY.md fact 2): the conv body has no backward')
-        if mfma_dtype not in ('fp32', 'fp32x3', 'fp16x2', 'bf16'):
-            raise ValueError("mfma_dtype must be 'fp32', 'fp32x3', 'fp16x2' or 'bf16'")
+        ar = self.arith = head_arith.plan(mfma_dtype)      # what each plan is: head_arith.PLANS
         L.load()
-        # 'fp32'  : every GEMM on v_mfma_f32_32x32x2_f32 (157 TFLOP/s peak).
-        # 'fp16x2' (default): fc6/fc7 forward, dgrad and wgrad on the f16 matrix cores, each fp32
-        #           operand a row-scaled hi + lo pair of f16 planes, 3 MFMA passes, fp32 accumulate
-        #           (csrc/gemm_x3.hip, naws_split_f16x2): as accurate as fp32x3 on every case of
-        #           tests/test_gpu_h2.py / profiles/r01_x3_accuracy.md, 1.6x faster.
-        # 'fp32x3': fc6/fc7 forward, dgrad and wgrad on the bf16 matrix cores with each fp32
-        #           operand split exactly into three bf16 planes and six MFMA passes
-        #           (csrc/gemm_x3.hip): fp32-accurate (tests/test_gpu_x3.py), ~1.65x faster.
-        #           The weight planes are re-split after every SGD update, on the update stream.
-        # 'bf16': conv2..conv5 and fc6/fc7 (forward, dgrad, wgrad) multiply in
-        # v_mfma_f32_32x32x16_bf16 with fp32 accumulation; parameters, activations, gradients,
-        # fc8, the dual softmax, the loss and the SGD update stay fp32 (BASELINE.json configs[3]:
-        # "bf16 MFMA conv/fc with fp32 loss")
         self.mfma_dtype = mfma_dtype
         self.C = num_classes - 1
         self.device = device
@@ -337,13 +322,11 @@ class WsddnEngine(object):
         # 97 us, tools/bench_fc8.py)
         self.FC8_KSPLIT = 4
         # entries of VGG16_CONVS each image runs before the deferred update is queued beside the
-        # chains (1: conv1_1; 2: conv1_1 + conv1_2 with pool1); fp32 / fp32x3 queue it before them
-        self.UPDATE_AFTER = 2 if mfma_dtype == 'bf16' else 1
-        self._update_behind_heads = mfma_dtype in ('fp16x2', 'bf16')
+        # chains (1: conv1_1; 2: conv1_1 + conv1_2 with pool1) where the plan queues it there
+        self.UPDATE_AFTER = max(1, ar.update_after)
+        self._update_behind_heads = ar.update_after > 0
         # fp16x2 plan: each image's proposals are pooled on that image's conv stream (conv_body)
         self.ROI_POOL_ON_CHAINS = True
-        # the 16-bit plans' RoIPoolF reads block-maxima maps of conv5_3, built beside the chains
-        self._roi_maps_on_chains = mfma_dtype in ('fp16x2', 'bf16')
         self._fc8_ws = None
         self._w6_updated = None      # the region table for the deferred kernel once fc6_w is done
         self._seg_ring = None
@@ -390,10 +373,19 @@ class WsddnEngine(object):
         i = next((k for k, e in enumerate(ends) if e > start), None)
         return i is not None and ends[i] >= start + count
 
+    def _head_views(self, flat):
+        """Both branches' fc6_w [8192, k6], fc6_b, fc7_w [2, 4096, 4096], fc7_b [2, 4096], fc8's weights
+        [2, 2C, 4096] and biases [2, 2C]: views of the arena `flat` (params, grads or momentum)."""
+        sp, C = self.arena.span, self.C
+        return (sp(flat, 'fc6_w', '_[noisy]_fc6_w').view(2 * HIDDEN, self.k6),
+                sp(flat, 'fc6_b', '_[noisy]_fc6_b'),
+                sp(flat, 'fc7_w', '_[noisy]_fc7_w').view(2, HIDDEN, HIDDEN),
+                sp(flat, 'fc7_b', '_[noisy]_fc7_b').view(2, HIDDEN),
+                sp(flat, 'fc8c_w', 'noisy_fc8d_w').view(2, 2 * C, HIDDEN),
+                sp(flat, 'fc8c_b', 'noisy_fc8d_b').view(2, 2 * C))
+
     def _weight_views(self):
-        w6 = self.arena.span(self.params, 'fc6_w', '_[noisy]_fc6_w').view(2 * HIDDEN, self.k6)
-        w7 = self.arena.span(self.params, 'fc7_w', '_[noisy]_fc7_w').view(2, HIDDEN, HIDDEN)
-        return w6, w7
+        return self._head_views(self.params)[0:3:2]
 
     # (what tools, tests and bench.py read of the operand planes, under the names they know)
     _wplanes = property(lambda self: getattr(self._fc, 'operands', None))     # w6 / w7 / w7t
@@ -401,18 +393,6 @@ class WsddnEngine(object):
     _rm_table = property(lambda self: getattr(self._fc, 'rm_table', None))
     _sgd_regions = property(lambda self: getattr(self._fc, 'whole', None))
     _sgd_regions_rest = property(lambda self: getattr(self._fc, 'rest', None))
-
-    def _refresh_weight_planes(self):
-        """fp16x2 / fp32x3 / bf16: re-split fc6_w / fc7_w (and fc7_w^T for the dgrad) into their
-        16-bit operand planes."""
-        if self._fc is None:
-            n6 = 2 * HIDDEN
-            o6, ob, o7 = (self.arena.offsets[k][0] for k in ('fc6_w', 'fc6_b', 'fc7_w'))
-            self._fc = FcPlanes(self.mfma_dtype, n6, self.k6, HIDDEN, o6, ob, o7, self.arena.total,
-                                self.device, self._one_hyper_run(o6, n6 * self.k6),
-                                self._one_hyper_run(o7, n6 * HIDDEN))
-        self._fc.split_all(*self._weight_views())
-        self._planes_dirty = False
 
     def grad_blob(self, name):
         return self.arena.view(self.grads, name)
@@ -610,7 +590,7 @@ class WsddnEngine(object):
         out = torch.empty((n, h, w, 512), device=self.device, dtype=torch.float32)
         # (bf16 plan: RoIPoolF writes fc6's one-plane operand over the same maps)
         self._roi_maps = ((torch.empty_like(out), torch.empty_like(out))
-                          if self._roi_maps_on_chains else None)
+                          if self.arith.roi_maps_on_chains else None)
         # the maps belong to THIS tensor in THIS state (_take_roi_maps)
         self._roi_maps_of = (out.data_ptr(), out._version)
         pooled = None
@@ -761,7 +741,7 @@ class WsddnEngine(object):
             return ops.roi_pool_f_f16x2(conv5, rois, self._amax5, self.roi_size, self.roi_size,
                                         self.spatial_scale, boost=obn_scores.reshape(-1),
                                         hier=True, maps=maps)
-        if self.mfma_dtype == 'bf16' and self.k6 % 64 == 0 and conv5.shape[-1] % 64 == 0:
+        if self.arith.roi_pool_slab and self.k6 % 64 == 0 and conv5.shape[-1] % 64 == 0:
             maps = self._take_roi_maps(conv5)
             if maps is None:
                 maps = (torch.empty_like(conv5), torch.empty_like(conv5))
@@ -772,114 +752,96 @@ class WsddnEngine(object):
                                   boost=obn_scores.reshape(-1), layout='NHWC', hier=True)
         return roi_feat.view(rois.shape[0], self.k6)
 
+    def _fc_operands(self):
+        """w6 / w7 / w7t as the plan's GEMM operands: fp32, the arena's own views; otherwise the
+        16-bit planes FcPlanes keeps, re-split first when a caller wrote the parameters."""
+        ar, (w6, w7) = self.arith, self._weight_views()
+        if not ar.planes16:
+            return dict(w6=ar.operand(w6), w7=ar.operand(w7), w7t=ar.operand(w7, transpose=True))
+        if self._fc is None:
+            n6 = 2 * HIDDEN
+            o6, ob, o7 = (self.arena.offsets[k][0] for k in ('fc6_w', 'fc6_b', 'fc7_w'))
+            self._fc = FcPlanes(ar, n6, self.k6, HIDDEN, o6, ob, o7, self.arena.total, self.device,
+                                self._one_hyper_run(o6, n6 * self.k6),
+                                self._one_hyper_run(o7, n6 * HIDDEN))
+        if self._planes_dirty:
+            self._fc.split_all(w6, w7)
+            self._planes_dirty = False
+        return self._fc.operands
+
     def head_forward(self, roi_feat, train, both_branches=True, pieces=None):
-        """roi_feat [Rt, k6] (or its F16x2 operand form) -> H6, H7 [Rt, nb*4096], logits L
-        [Rt, nb*2C].  pieces: see _join_update_for_head (the pipelined update's events)."""
-        f16p = isinstance(roi_feat, ops.F16x2)
-        # (the bf16 plan's operand form, written by the pooling kernel: bf16 [k6/16, Rt, 16])
-        slab_x = not f16p and roi_feat.dtype == torch.bfloat16 and roi_feat.dim() == 3
-        rt = roi_feat.planes.shape[-2] if f16p else (roi_feat.shape[1] if slab_x else roi_feat.shape[0])
+        """roi_feat [Rt, k6] (or its operand form, written by the pooling kernel) -> H6, H7
+        [Rt, nb*4096], logits L [Rt, nb*2C].  pieces: see _join_update_for_head (the pipelined
+        update's events)."""
+        ar = self.arith
         nb = 2 if both_branches else 1
-        C = self.C
-        w6 = self.arena.span(self.params, 'fc6_w', '_[noisy]_fc6_w').view(2 * HIDDEN, self.k6)
-        b6 = self.arena.span(self.params, 'fc6_b', '_[noisy]_fc6_b')
-        w7 = self.arena.span(self.params, 'fc7_w', '_[noisy]_fc7_w').view(2, HIDDEN, HIDDEN)
-        b7 = self.arena.span(self.params, 'fc7_b', '_[noisy]_fc7_b').view(2, HIDDEN)
-        w8 = self.arena.span(self.params, 'fc8c_w', 'noisy_fc8d_w').view(2, 2 * C, HIDDEN)
-        b8 = self.arena.span(self.params, 'fc8c_b', 'noisy_fc8d_b').view(2, 2 * C)
+        _w6, b6, _w7, b7, w8, b8 = self._head_views(self.params)
         drop = train and self.dropout > 0
-        epi = L.EPI_BIAS_RELU_DROP if drop else L.EPI_BIAS_RELU
-        bf = self.mfma_dtype == 'bf16'
-        x3 = self.mfma_dtype == 'fp32x3'
-        h2 = self.mfma_dtype == 'fp16x2'
-        if pieces is not None and not (h2 and nb == 2):
+        epi6, epi7 = (dict(epilogue=L.EPI_BIAS_RELU_DROP if drop else L.EPI_BIAS_RELU, bias=b,
+                           drop_ratio=self.dropout if drop else 0.0, seed=self._seed(layer))
+                      for layer, b in ((6, b6), (7, b7)))
+        if pieces is not None and not (ar.reports_maxima and nb == 2):
             self._finish_pieces(pieces)      # (a caller's own plan: join the whole update first)
             pieces = None
-        if self.mfma_dtype != 'fp32' and self._planes_dirty:
-            self._refresh_weight_planes()
+        W = self._fc_operands()
         # the activation operand in the plan's form (its own kernels, outside the timed launch)
-        if h2:
-            xp = roi_feat if isinstance(roi_feat, ops.F16x2) else ops.split_f16x2(roi_feat)
-        elif x3:
-            xp = roi_feat if roi_feat.dtype == torch.bfloat16 else ops.split_bf16x3(roi_feat)
-        elif bf:
-            xp = roi_feat if slab_x else ops.to_bf16_slab(roi_feat)
+        xp = ar.operand(roi_feat)
         # bench.py: HIP events around the dominant kernel (piece by piece: around each piece)
         with self._timed('timing_events', on=pieces is None):
-            if h2 and pieces is not None:
-                # fc6 forward piece by piece: piece (r0, r1) = weight rows / h6 columns r0..r1 of one
-                # branch, launched behind the event of ITS update; same kernel, same K order, same
-                # Dropout counters as the one launch below (naws_gemm_f32_f16x2_nt_cols)
-                self._new_amax_arena(rt, nb)
-                sc6n = self._scales(nb, rt)
-                sc6t = self._scales(nb, HIDDEN) if train else None
-                h6 = torch.empty((rt, nb * HIDDEN), device=self.device, dtype=torch.float32)
-                main = torch.cuda.current_stream(self.device)
-                rowwords = ops.amax_words(sc6n)                       # [nb, Rt]
-                colwords = None if sc6t is None else ops.amax_words(sc6t).view(-1)
-                for r0, r1, ev in pieces['fc6']:
-                    main.wait_event(ev)
-                    if r0 // HIDDEN != (r1 - 1) // HIDDEN:
-                        raise RuntimeError('a forward piece must lie inside one branch')
-                    with self._timed('timing_events'):
-                        ops.gemm_f32_f16x2_nt_cols(
-                            xp, self._wplanes['w6'].rows(r0, r1), h6[:, r0:r1], r0, nb * HIDDEN,
-                            epilogue=epi, bias=b6[r0:r1], drop_ratio=self.dropout if drop else 0.0,
-                            seed=self._seed(6), rowmax=rowwords[r0 // HIDDEN], rowmax_seg=HIDDEN,
-                            colmax=None if colwords is None else colwords[r0:r1])
-                self._finish_pieces(pieces)          # fc7 / fc8 read the rest of the update
-            elif h2:
-                # the GEMM epilogue reports max|h6| per row of each branch (fc7's operand scale) and,
-                # in training, per column (fc7 wgrad's): no pass over h6 for the maxima
-                self._new_amax_arena(rt, nb)
-                sc6n = self._scales(nb, rt)
-                sc6t = self._scales(nb, HIDDEN) if train else None
-                h6 = ops.gemm_f32_f16x2_nt(xp, self._wplanes['w6'].rows(0, nb * HIDDEN), epilogue=epi,
-                                           bias=b6, drop_ratio=self.dropout if drop else 0.0,
-                                           seed=self._seed(6), rowmax=ops.amax_words(sc6n),
-                                           rowmax_seg=HIDDEN,
-                                           colmax=None if sc6t is None else ops.amax_words(sc6t))
-            elif x3:
-                h6 = ops.gemm_f32x3_nt(xp, self._wplanes['w6'][:, :, :nb * HIDDEN], epilogue=epi,
-                                       bias=b6, drop_ratio=self.dropout if drop else 0.0,
-                                       seed=self._seed(6))
-            elif bf:
-                h6 = ops.gemm_bf16_slab_nt(xp, self._wplanes['w6'][:, :nb * HIDDEN], epilogue=epi, bias=b6,
-                                           drop_ratio=self.dropout if drop else 0.0, seed=self._seed(6))
+            if ar.reports_maxima:
+                h6, sc6n, sc6t = self._fc6_forward_maxima(xp, W['w6'], nb, train, epi6, pieces)
             else:
-                h6 = ops.gemm(roi_feat, w6[:nb * HIDDEN], False, True, epilogue=epi, bias=b6,
-                              drop_ratio=self.dropout if drop else 0.0, seed=self._seed(6))
+                h6 = ar.gemm_nt(xp, ar.rows(W['w6'], 0, nb * HIDDEN), **epi6)
         xp = None
+        rt = h6.shape[0]
         h6v = h6.view(rt, nb, HIDDEN).permute(1, 0, 2)       # [nb, Rt, 4096] strided views
         h7 = torch.empty((rt, nb * HIDDEN), device=self.device, dtype=torch.float32)
         h7v = h7.view(rt, nb, HIDDEN).permute(1, 0, 2)
-        if h2:
+        if ar.reports_maxima:
             # one pass over h6 writes both operand forms (rows for fc7, columns for fc7's wgrad)
             h6n, self._h6t = ops.split_f16x2_dual(h6v, sc6n, sc6t)
-            ops.gemm_f32_f16x2_nt(h6n, self._wplanes['w7'].batches(nb), out=h7v,
-                                  epilogue=epi, bias=b7, drop_ratio=self.dropout if drop else 0.0,
-                                  seed=self._seed(7))
-            del h6n
-        elif x3:
-            ops.gemm_f32x3_nt(ops.split_bf16x3(h6v), self._wplanes['w7'][:, :nb], out=h7v,
-                              epilogue=epi, bias=b7, drop_ratio=self.dropout if drop else 0.0,
-                              seed=self._seed(7))
-        elif bf:
-            ops.gemm_bf16_slab_nt(ops.to_bf16_slab(h6v), self._wplanes['w7'][:nb], out=h7v,
-                                  epilogue=epi, bias=b7, drop_ratio=self.dropout if drop else 0.0,
-                                  seed=self._seed(7))
         else:
-            ops.gemm(h6v, w7[:nb], False, True, out=h7v, epilogue=epi, bias=b7,
-                     drop_ratio=self.dropout if drop else 0.0, seed=self._seed(7))
+            h6n = ar.operand(h6v)
+        ar.gemm_nt(h6n, ar.batches(W['w7'], nb), out=h7v, **epi7)
+        del h6n
         # logits [Rt, nb * ld8]: branch b holds fc8c | fc8d in columns b*ld8 .. b*ld8 + 2C.  ld8 = 2C
         # rounded up to 4 floats so the batch-2 GEMM operands stay 16-byte aligned for any class
         # count (odd C: the weights / bias are copied into zero-padded [ld8, 4096] operands)
-        ld8 = self.ld8
         w8g, b8g = self._fc8_operands(w8, b8)
-        lg = torch.empty((rt, nb * ld8), device=self.device, dtype=torch.float32)
-        lgv = lg.view(rt, nb, ld8).permute(1, 0, 2)
+        lg = torch.empty((rt, nb * self.ld8), device=self.device, dtype=torch.float32)
+        lgv = lg.view(rt, nb, self.ld8).permute(1, 0, 2)
         self._fc8_gemm(h7v, w8g[:nb], False, True, lgv, L.EPI_BIAS, b8g)
         return h6, h7, lg
+
+    def _fc6_forward_maxima(self, xp, w6, nb, train, epi, pieces):
+        """fp16x2's fc6 forward: the GEMM epilogue reports max|h6| per row of each branch (fc7's
+        operand scale) and, in training, per column (fc7 wgrad's) - no pass over h6 for them.
+        Returns h6 and the two scale blocks.  pieces (the pipelined update): piece (r0, r1) = weight
+        rows / h6 columns r0..r1 of one branch, launched behind the event of ITS update; same kernel,
+        same K order, same Dropout counters as the one launch (naws_gemm_f32_f16x2_nt_cols)."""
+        ar, rt = self.arith, xp.planes.shape[-2]
+        self._new_amax_arena(rt, nb)
+        sc6n = self._scales(nb, rt)
+        sc6t = self._scales(nb, HIDDEN) if train else None
+        rowwords = ops.amax_words(sc6n)                       # [nb, Rt]
+        colwords = None if sc6t is None else ops.amax_words(sc6t)
+        if pieces is None:
+            h6 = ar.gemm_nt(xp, ar.rows(w6, 0, nb * HIDDEN), rowmax=rowwords, rowmax_seg=HIDDEN,
+                            colmax=colwords, **epi)
+            return h6, sc6n, sc6t
+        h6 = torch.empty((rt, nb * HIDDEN), device=self.device, dtype=torch.float32)
+        main = torch.cuda.current_stream(self.device)
+        for r0, r1, ev in pieces['fc6']:
+            main.wait_event(ev)
+            if r0 // HIDDEN != (r1 - 1) // HIDDEN:
+                raise RuntimeError('a forward piece must lie inside one branch')
+            with self._timed('timing_events'):
+                ops.gemm_f32_f16x2_nt_cols(
+                    xp, ar.rows(w6, r0, r1), h6[:, r0:r1], r0, nb * HIDDEN,
+                    **dict(epi, bias=epi['bias'][r0:r1]), rowmax=rowwords[r0 // HIDDEN],
+                    rowmax_seg=HIDDEN, colmax=None if colwords is None else colwords.view(-1)[r0:r1])
+        self._finish_pieces(pieces)          # fc7 / fc8 read the rest of the update
+        return h6, sc6n, sc6t
 
     def _fc8_gemm(self, a, b, trans_a, trans_b, out, epilogue=L.EPI_NONE, bias=None):
         """fc8's products have a small output and a long inner dimension (K = 4096 forward,
@@ -980,84 +942,57 @@ class WsddnEngine(object):
         return out
 
     def _head_backward(self, x, h6, h7, dl, fuse_update=False):
-        C, rt = self.C, h6.shape[0]
-        G = self.grads
+        C, rt, G = self.C, h6.shape[0], self.grads
         scale = 1.0 / (1.0 - self.dropout) if self.dropout > 0 else 1.0
-        w7 = self.arena.span(self.params, 'fc7_w', '_[noisy]_fc7_w').view(2, HIDDEN, HIDDEN)
-        w8 = self.arena.span(self.params, 'fc8c_w', 'noisy_fc8d_w').view(2, 2 * C, HIDDEN)
-        gw6 = self.arena.span(G, 'fc6_w', '_[noisy]_fc6_w').view(2 * HIDDEN, self.k6)
-        gb6 = self.arena.span(G, 'fc6_b', '_[noisy]_fc6_b')
-        gw7 = self.arena.span(G, 'fc7_w', '_[noisy]_fc7_w').view(2, HIDDEN, HIDDEN)
-        gb7 = self.arena.span(G, 'fc7_b', '_[noisy]_fc7_b')
-        gw8 = self.arena.span(G, 'fc8c_w', 'noisy_fc8d_w').view(2, 2 * C, HIDDEN)
-        gb8 = self.arena.span(G, 'fc8c_b', 'noisy_fc8d_b')
-        ld8 = self.ld8
-        pad = ld8 != 2 * C
-        dlv = dl.view(rt, 2, ld8).permute(1, 0, 2)             # [2, Rt, ld8]
-        h7v = h7.view(rt, 2, HIDDEN).permute(1, 0, 2)
-        h6v = h6.view(rt, 2, HIDDEN).permute(1, 0, 2)
-        bf = self.mfma_dtype == 'bf16'
-        x3 = self.mfma_dtype == 'fp32x3'
-        h2 = self.mfma_dtype == 'fp16x2'
+        gw6, gb6, gw7, gb7, gw8, gb8 = self._head_views(G)
+        ld8, pad = self.ld8, self.ld8 != 2 * C
+        dz7, dz6 = torch.empty_like(h7), torch.empty_like(h6)
+        dlv, h7v, h6v, dz7v, dz6v = (t.view(rt, 2, -1).permute(1, 0, 2)      # [2, Rt, ld8 | 4096]
+                                     for t in (dl, h7, h6, dz7, dz6))
+        ar, amax = self.arith, self.arith.reports_maxima
+        W = self._fc_operands()
         red = self.reducer
+        # x: the pooling kernel's own operand (fp16x2 planes with per-roi scales, the bf16 slab), or a
+        # caller's fp32 features
+        pooled = ar.is_operand(x)
         # Order: the data-gradient chain first, then fc6_w's gradient (86 % of the all-reduce
         # bytes) so that its exchange starts as early as possible, the small gradients last.
         # 1. dZ7 = dL W8 and dZ6 = dZ7 W7, each gated by the ReLU / Dropout of its layer
-        w8g = w8
-        if pad:
-            w8g = self._fc8_operands(w8, self.arena.span(self.params, 'fc8c_b', 'noisy_fc8d_b')
-                                     .view(2, 2 * C))[0]
-        dz7 = torch.empty_like(h7)
-        dz7v = dz7.view(rt, 2, HIDDEN).permute(1, 0, 2)
-        dz6 = torch.empty_like(h6)
-        dz6v = dz6.view(rt, 2, HIDDEN).permute(1, 0, 2)
-        planes_x = h2 and isinstance(x, ops.F16x2)
-        if h2:
+        w8g = self._fc8_operands(*self._head_views(self.params)[4:])[0]      # (ld8 rows when padded)
+        amax7, gate6 = {}, dict(epilogue=L.EPI_GATE_POS, aux=h6v, alpha=scale)
+        if amax:
             # every GEMM reports the maxima its consumer's operand split needs; each of dZ7 / dZ6
-            # is then read once by a split that writes all the forms in which it is multiplied
+            # is then read once by a split that writes all the forms in which it is multiplied.
+            # x's planes carry per-roi scales s_r: dW6 = sum_r (dZ6[r] / s_r) (x[r] s_r), so dZ6's
+            # column maxima are taken over dZ6[r] / s_r (exact: powers of two)
             sc7n, sc7t, sc6t = self._scales(2, rt), self._scales(2, HIDDEN), self._scales(1, 2 * HIDDEN)
             amax7 = dict(rowmax=ops.amax_words(sc7n), colmax=ops.amax_words(sc7t))
-        else:
-            amax7 = {}
+            rowmul = x.inv_scale if pooled else None
+            gate6.update(colmax=ops.amax_words(sc6t), colmax_rowmul=rowmul)
         ops.gemm(dlv, w8g, False, False, out=dz7v, epilogue=L.EPI_GATE_POS, aux=h7v, alpha=scale,
                  **amax7)
-        if h2:
+        # dX = dZ W: W^T's operand is kept beside W's
+        if amax:
             dz7n, dz7t = ops.split_f16x2_dual(dz7v, sc7n, sc7t)
-            # dX = dZ W: W^T planes are kept beside the W planes.  x's planes carry per-roi scales
-            # s_r: dW6 = sum_r (dZ6[r] / s_r) (x[r] s_r), so dZ6's column maxima are taken over
-            # dZ6[r] / s_r (exact: powers of two)
-            ops.gemm_f32_f16x2_nt(dz7n, self._wplanes['w7t'], out=dz6v,
-                                  epilogue=L.EPI_GATE_POS, aux=h6v, alpha=scale,
-                                  colmax=ops.amax_words(sc6t),
-                                  colmax_rowmul=x.inv_scale if planes_x else None)
-            del dz7n
-        elif x3:
-            ops.gemm_f32x3_nt(ops.split_bf16x3(dz7v), self._wplanes['w7t'], out=dz6v,
-                              epilogue=L.EPI_GATE_POS, aux=h6v, alpha=scale)
-        elif bf:
-            ops.gemm_bf16_slab_nt(ops.to_bf16_slab(dz7v), self._wplanes['w7t'], out=dz6v,
-                                  epilogue=L.EPI_GATE_POS, aux=h6v, alpha=scale)
         else:
-            ops.gemm(dz7v, w7, False, False, out=dz6v, epilogue=L.EPI_GATE_POS, aux=h6v,
-                     alpha=scale)
+            dz7n = ar.operand(dz7v)
+        ar.gemm_nt(dz7n, W['w7t'], out=dz6v, **gate6)
+        del dz7n
         # 2. fc6: dW = dZ6^T X in row chunks (both operands K(=rows)-contiguous through the
         # transposing split); each chunk's all-reduce starts while the next one is computed
-        if h2:
+        if amax:
             # planes [2, Rt/16, 8192, 16] of (diag(1/s_r) dZ6)^T
-            dz6t = ops.split_f16x2_dual(dz6, None, sc6t.view(2, 2 * HIDDEN),
-                                        rowmul=x.inv_scale if planes_x else None)[1]
-            # x^T: the pooling kernel's planes are read as they are, through transposing LDS reads
-            # (csrc/gemm_btr.hip); fp32 features (a caller's own roi_feat) are split transposed
-            xk = planes_x
-            xt = None if xk else ops.split_f16x2(x, transpose=True)    # [2, Rt/16, 25088, 16]
-        elif x3:
-            dz6t = ops.split_bf16x3(dz6, transpose=True)       # [3, Rt/16, 8192, 16]
-            xt = ops.split_bf16x3(x, transpose=True)           # [3, Rt/16, 25088, 16]
-        elif bf:
-            dz6t = ops.to_bf16_slab(dz6, transpose=True)       # [Rt/16, 8192, 16]
-            # [Rt/16, 25088, 16]: from the pooling kernel's own operand, or a caller's fp32 features
-            xt = (ops.bf16_slab_transpose(x) if x.dtype == torch.bfloat16
-                  else ops.to_bf16_slab(x, transpose=True))
+            dz6t = ops.split_f16x2_dual(dz6, None, sc6t.view(2, 2 * HIDDEN), rowmul=rowmul)[1]
+        else:
+            dz6t = ar.operand(dz6, transpose=True)             # [(3,) Rt/16, 8192, 16]
+        # x^T [.., Rt/16, 25088, 16]: a caller's fp32 features are split transposed; the pooling
+        # kernel's planes are read as they are, through transposing LDS reads (fp16x2:
+        # csrc/gemm_btr.hip), or transposed plane to plane (bf16)
+        if not pooled:
+            xt = ar.operand(x, transpose=True)
+        else:
+            xt = None if amax else ops.bf16_slab_transpose(x)
+        fuse = fuse_update and self._can_fuse_wgrad_update() and (pooled or not amax)
         pipelined = self._pipelined()
         plan = message_plan(self.arena, 2 * HIDDEN, self.allreduce_chunks, red.active, pipelined)
         self._pipe_sent = pipelined
@@ -1088,30 +1023,13 @@ class WsddnEngine(object):
         next_piece = 0
         for kind, rows in plan[:-1]:
             r0, r1 = rows
-            if h2:
-                # 25088 = 98 column tiles of 256: 32 x 98 = 12.25 waves of 256 CUs.  96 column
-                # tiles make 12 full waves; the last 512 columns go out as one wave of 128x128 tiles
-                ncut = self._wgrad_column_cut(r1 - r0)
-                if xk and fuse_update and self._can_fuse_wgrad_update():
-                    self._wgrad_update_w6(dz6t, x, r0, r1, ncut)
-                elif xk:
-                    for c0, c1 in (((0, ncut), (ncut, self.k6)) if ncut else ((0, self.k6),)):
-                        ops.gemm_f32_f16x2_nt_xk(dz6t.rows(r0, r1), x, ncols=(c0, c1),
-                                                 out=gw6[r0:r1, c0:c1])
-                elif ncut:
-                    ops.gemm_f32_f16x2_nt(dz6t.rows(r0, r1), xt.rows(0, ncut), out=gw6[r0:r1, :ncut])
-                    ops.gemm_f32_f16x2_nt(dz6t.rows(r0, r1), xt.rows(ncut, self.k6),
-                                          out=gw6[r0:r1, ncut:])
-                else:
-                    ops.gemm_f32_f16x2_nt(dz6t.rows(r0, r1), xt, out=gw6[r0:r1])
-            elif x3:
-                ops.gemm_f32x3_nt(dz6t[:, :, r0:r1], xt, out=gw6[r0:r1])
-            elif bf and fuse_update and self._can_fuse_wgrad_update():
-                self._wgrad_update_w6_bf16(dz6t, xt, r0, r1)
-            elif bf:
-                ops.gemm_bf16_slab_nt(dz6t[:, r0:r1], xt, out=gw6[r0:r1])
+            a = ar.rows(dz6t, r0, r1)
+            if amax:
+                self._fc6_wgrad_cut(a, x, xt, gw6, r0, r1, fuse)
+            elif fuse:
+                self._wgrad_update_w6(a, xt, r0, r1)
             else:
-                ops.gemm(dz6[:, r0:r1], x, True, False, out=gw6[r0:r1])
+                ar.gemm_nt(a, xt, out=gw6[r0:r1])
             blocks = self._shard_blocks()
             if blocks is None:
                 red.reduce_async(message_slice(self.arena, G, kind, rows, self.k6))
@@ -1126,23 +1044,18 @@ class WsddnEngine(object):
         # fc8 dW = dL^T H7, db
         if not pipelined:
             ops.colsum(dz6, out=gb6)
-        if h2:
-            ops.gemm_f32_f16x2_nt(dz7t, self._h6t, out=gw7)
-            self._h6t = None
-        elif x3:
-            ops.gemm_f32x3_nt(ops.split_bf16x3(dz7v, transpose=True),
-                              ops.split_bf16x3(h6v, transpose=True), out=gw7)
-        elif bf:
-            ops.gemm_bf16_slab_nt(ops.to_bf16_slab(dz7v, transpose=True),
-                                  ops.to_bf16_slab(h6v, transpose=True), out=gw7)
+        if amax:
+            a7, h6t, self._h6t = dz7t, self._h6t, None
         else:
-            ops.gemm(dz7v, h6v, True, False, out=gw7)
+            a7, h6t = ar.operand(dz7v, transpose=True), ar.operand(h6v, transpose=True)
+        ar.gemm_nt(a7, h6t, out=gw7)
+        del a7, h6t
         ops.colsum(dz7, out=gb7)
         if pad:
             gw8p = torch.empty((2, ld8, HIDDEN), device=self.device, dtype=torch.float32)
             self._fc8_gemm(dlv, h7v, True, False, gw8p)
             gw8.copy_(gw8p[:, :2 * C])
-            gb8.view(2, 2 * C).copy_(ops.colsum(dl).view(2, ld8)[:, :2 * C])
+            gb8.copy_(ops.colsum(dl).view(2, ld8)[:, :2 * C])
         else:
             self._fc8_gemm(dlv, h7v, True, False, gw8)
             ops.colsum(dl, out=gb8)
@@ -1156,48 +1069,50 @@ class WsddnEngine(object):
 
     def _can_fuse_wgrad_update(self):
         return (self.fuse_wgrad_update and not self.reducer.active and self.iter_size == 1
-                and self.mfma_dtype in ('fp16x2', 'bf16') and self.fused_planes
+                and self.arith.wgrad_update and self.fused_planes
                 and self._pipe_planes_ok() and self.k6 % 256 == 0)
 
-    def _w6_sgd_args(self):
-        """For the update in fc6_w's wgrad epilogue: fc6_w, its momentum, and the kernels' SGD
-        arguments lr .. iter_count; raises unless both branches share one hyper-parameter run."""
-        ends, lr_mult, wd = self._seg_host
-        o6, n6 = self.arena.offsets['fc6_w'][0], 2 * HIDDEN
-        sg = next(i for i, e in enumerate(ends) if e > o6)
-        if ends[sg] < o6 + n6 * self.k6:
-            raise RuntimeError('fc6_w and _[noisy]_fc6_w lie in different hyper-parameter runs')
-        m6 = self.arena.span(self.momentum_buf, 'fc6_w', '_[noisy]_fc6_w').view(n6, self.k6)
-        return self._weight_views()[0], m6, (self.lr, lr_mult[sg], wd[sg], self.momentum, 0,
-                                             self.gpu_num, self.sgd_iter_count)
+    def _fc6_wgrad_cut(self, a, x, xt, gw6, r0, r1, fuse):
+        """fp16x2: rows r0..r1 of fc6_w's gradient (a: those rows of dZ6^T's operand; xt: x^T's, or
+        None: x is the pooling kernel's operand, read as it is) or, `fuse`, their update.  25088 =
+        98 column tiles of 256: 32 x 98 = 12.25 waves of 256 CUs.  96 column tiles make 12 full
+        waves; the last 512 columns go out as one wave of 128x128 tiles."""
+        ncut = self._wgrad_column_cut(r1 - r0)
+        cuts = ((0, ncut), (ncut, self.k6)) if ncut else ((0, self.k6),)
+        if fuse:
+            return self._wgrad_update_w6(a, x, r0, r1, cuts)
+        for c0, c1 in cuts:
+            if xt is None:
+                ops.gemm_f32_f16x2_nt_xk(a, x, ncols=(c0, c1), out=gw6[r0:r1, c0:c1])
+            else:
+                self.arith.gemm_nt(a, self.arith.rows(xt, c0, c1), out=gw6[r0:r1, c0:c1])
 
-    def _wgrad_update_w6(self, dz6t, x, r0, r1, ncut):
-        """fc6_w's rows r0..r1: wgrad GEMM with the SGD update + the rows' operand planes in its
-        epilogue (ops.gemm_f32_f16x2_nt_xk_sgd), on the main stream.  First chunk: the rows' maxima
-        become the bounds of this update; last chunk: the conditional exact re-split."""
-        fc, tag = self._fc, self.sgd_iter_count + 1
-        w6, m6, sgd = self._w6_sgd_args()
-        if r0 == 0:
-            fc.begin(ALL, with7=False)
-        for c0, c1 in (((0, ncut), (ncut, self.k6)) if ncut else ((0, self.k6),)):
-            ops.gemm_f32_f16x2_nt_xk_sgd(dz6t.rows(r0, r1), x, w6, m6, *sgd, fc.operands['w6'].planes,
-                                         fc.bound(6), fc.maxima(6), fc.inv_scale(6), fc.ovf, tag,
-                                         ncols=(c0, c1), rows=(r0, r1))
-        if r1 == 2 * HIDDEN:
-            fc.resplit6(w6, ALL, fc.ovf, tag)
+    def _wgrad_update_w6(self, a, x, r0, r1, cuts=None):
+        """fc6_w's rows r0..r1 updated (parameters, momentum, operand planes) in the epilogue of
+        their wgrad GEMM, on the main stream.  fp16x2 (cuts: the column ranges, x: the pooling
+        kernel's planes): the first chunk makes the rows' maxima the bounds of this update, the last
+        one queues the conditional exact re-split.  bf16 (x: x^T's slab): one rounded plane, no
+        scales, nothing to bound or re-split."""
+        fc, tag, (ends, lr_mult, wd) = self._fc, self.sgd_iter_count + 1, self._seg_host
+        o6, last = self.arena.offsets['fc6_w'][0], r1 == 2 * HIDDEN
+        sg = next(i for i, e in enumerate(ends) if e > o6)      # (one run: _can_fuse_wgrad_update)
+        w6, m6 = self._weight_views()[0], self._head_views(self.momentum_buf)[0]
+        sgd = (self.lr, lr_mult[sg], wd[sg], self.momentum, 0, self.gpu_num, self.sgd_iter_count)
+        if cuts is None:
+            ops.gemm_bf16_slab_nt_sgd(a, x, w6, m6, *sgd, fc.operands['w6'], rows=(r0, r1))
+        else:
+            if r0 == 0:
+                fc.begin(ALL, with7=False)
+            for c0, c1 in cuts:
+                ops.gemm_f32_f16x2_nt_xk_sgd(a, x, w6, m6, *sgd, fc.operands['w6'].planes,
+                                             fc.bound(6), fc.maxima(6), fc.inv_scale(6), fc.ovf, tag,
+                                             ncols=(c0, c1), rows=(r0, r1))
+            if last:
+                fc.resplit6(w6, ALL, fc.ovf, tag)
+        if last:
             # the route is decided HERE: the deferred kernel of this step must skip fc6_w whatever
             # the toggles say by the time it runs (the table to use travels with the flag)
             self._w6_updated = fc.rest
-
-    def _wgrad_update_w6_bf16(self, dz6t, xt, r0, r1):
-        """The bf16 plan's form of _wgrad_update_w6: fc6_w's rows r0..r1 updated (parameters,
-        momentum, the rounded operand plane) in the epilogue of their weight-gradient GEMM
-        (ops.gemm_bf16_slab_nt_sgd); no scales, nothing to bound or re-split."""
-        w6, m6, sgd = self._w6_sgd_args()
-        ops.gemm_bf16_slab_nt_sgd(dz6t[:, r0:r1], xt, w6, m6, *sgd, self._fc.operands['w6'],
-                                  rows=(r0, r1))
-        if r1 == 2 * HIDDEN:
-            self._w6_updated = self._fc.rest
 
     def train_step(self, data, rois, obn_scores, labels_oh, seg=None):
         """forward_backward + sgd_step as one call.  With no gradient exchange between the two
@@ -1312,7 +1227,7 @@ class WsddnEngine(object):
         if want is None:
             want = True
         on = bool(want and self.reducer.active and hasattr(self.reducer, 'wait_first')
-                  and self.mfma_dtype == 'fp16x2'
+                  and self.arith.reports_maxima
                   and not self.sharded_update and self.iter_size == 1 and self.k6 % 256 == 0
                   and self.fused_planes and (self.defer_update is None or self.defer_update))
         if on and not self._pipe_warned:
@@ -1341,34 +1256,25 @@ class WsddnEngine(object):
             self.wait_allreduce()
         if self._shard_blocks() is not None:
             return self._apply_update_sharded()
-        fc = self._fc
+        fc, scaled = self._fc, self.arith.reports_maxima
+        rest, self._w6_updated = self._w6_updated, None
+        w6_done = rest is not None
+        # fc6_w (weights, momentum, planes) was updated by its wgrad GEMM in this step's backward:
+        # the rest MUST take the plane-writing kernel with fc6_w's region skipped, even if an A/B
+        # tool has flipped fused_planes since
+        if w6_done and (fc is None or self._sgd_regions is None or not self.arith.wgrad_update):
+            raise RuntimeError('fc6_w was updated in its wgrad epilogue but the plane state '
+                               'it belongs to is gone (engine toggles changed mid-step?)')
+        # the SGD kernel writes the planes too (a region table exists: fc is there, k6 % 256 == 0;
+        # planes marked dirty - a caller wrote through blob() - carry stale maxima: that update
+        # takes the exact route below); fp32x3 / bf16: the same kernel with their plane formats
+        writes = w6_done or (self.fused_planes and self._sgd_regions is not None
+                             and self.iter_size == 1 and not self._planes_dirty)
+        planes, planes_bf = writes and scaled, writes and not scaled
         # fp16x2: the SGD kernel reports max|w| of every updated fc6_w / fc7_w row into the scale
         # blocks of their operand planes, so the re-split reads the weights once (k6 % 256: a
         # wave's 256 floats stay in one row)
-        fused = (self.mfma_dtype == 'fp16x2' and fc is not None
-                 and self.iter_size == 1 and self.k6 % 256 == 0)
-        # (planes marked dirty - a caller wrote through blob() - carry stale maxima: that update
-        # takes the exact route below)
-        planes = (fused and self.fused_planes and self._sgd_regions is not None
-                  and not self._planes_dirty)
-        # fp32x3 / bf16: the same kernel with their plane formats (no maxima involved)
-        planes_bf = (self.mfma_dtype in ('fp32x3', 'bf16') and self.fused_planes
-                     and self._sgd_regions is not None and self.iter_size == 1
-                     and not self._planes_dirty and fc is not None)
-        rest, self._w6_updated = self._w6_updated, None
-        w6_done = rest is not None
-        if w6_done:
-            # fc6_w (weights, momentum, planes) was updated by its wgrad GEMM in this step's
-            # backward: the rest MUST take the plane-writing kernel with fc6_w's region skipped,
-            # even if an A/B tool has flipped fused_planes since
-            if (fc is None or self._sgd_regions is None
-                    or self.mfma_dtype not in ('fp16x2', 'bf16')):
-                raise RuntimeError('fc6_w was updated in its wgrad epilogue but the plane state '
-                                   'it belongs to is gone (engine toggles changed mid-step?)')
-            if self.mfma_dtype == 'bf16':
-                planes_bf = True
-            else:
-                fused = planes = True
+        fused = planes or (scaled and fc is not None and self.iter_size == 1 and self.k6 % 256 == 0)
         regions = rest if w6_done else self._sgd_regions
         w6, w7 = self._weight_views()
         tag = self.sgd_iter_count + 1
@@ -1524,7 +1430,7 @@ class WsddnEngine(object):
         if not (self.sharded_update and self.reducer.active):
             return None
         if self._shard is None:
-            if self.mfma_dtype != 'fp16x2' or self.iter_size != 1 or self.k6 % 256 != 0:
+            if not self.arith.reports_maxima or self.iter_size != 1 or self.k6 % 256 != 0:
                 raise NotImplementedError('NAWS.SHARDED_UPDATE needs the fp16x2 plan, ITER_SIZE 1 '
                                           'and a 256-multiple fc6 input')
             blocks = owner_blocks(2 * HIDDEN, self.reducer.world_size)

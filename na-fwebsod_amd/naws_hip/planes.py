@@ -7,7 +7,7 @@ and `bound` name its parts, and nothing outside this module indexes it."""
 
 import torch
 
-from . import lib as L
+from . import head_arith
 from . import ops
 
 SKIP_ROWS = 32      # reducer.owner_blocks cuts fc6_w in multiples of this: a skipped block's batch
@@ -17,28 +17,26 @@ ALL = 'all'         # every row of fc6_w, for begin() / resplit6()
 class FcPlanes(object):
     def __init__(self, plan, rows6, k6, hidden, o6, ob, o7, total, device, one_run6=True,
                  one_run7=True):
-        """plan: the engine's mfma_dtype; o6 / ob / o7 / total: first arena element of fc6_w / fc6_b
-        / fc7_w and the arena's length; one_run6 / one_run7: the matrix has ONE (lr_mult, weight
-        decay).  Allocates and launches nothing: split_all() fills the planes."""
-        if plan not in ('fp16x2', 'fp32x3', 'bf16'):
-            raise ValueError('the %r plan has no operand planes' % (plan,))
-        self.plan, self.rows6, self.k6, self.hidden = plan, rows6, k6, hidden
+        """plan: the engine's mfma_dtype (or its head_arith object); o6 / ob / o7 / total: first arena
+        element of fc6_w / fc6_b / fc7_w and the arena's length; one_run6 / one_run7: the matrix has
+        ONE (lr_mult, weight decay).  Allocates and launches nothing: split_all() fills the planes."""
+        ar = self.arith = head_arith.plan(plan)
+        if not ar.planes16:
+            raise ValueError('the %r plan has no operand planes' % (ar.name,))
+        self.rows6, self.k6, self.hidden = rows6, k6, hidden
         self.o6, self.ob, self.o7, self.total, self.all6 = o6, ob, o7, total, (0, rows6)
         nb = rows6 // hidden
-        self.convert = {'fp16x2': ops.split_f16x2, 'fp32x3': ops.split_bf16x3}.get(plan, ops.to_bf16_slab)
-        self.fmt = {'fp16x2': L.PLANES_F16X2, 'fp32x3': L.PLANES_BF16X3}.get(plan, L.PLANES_BF16)
-        kpad = {'fp16x2': 32, 'fp32x3': 16}.get(plan, 64)
-        s6, s7 = (-(-k6 // kpad) * kpad // 16, rows6, 16), (nb, -(-hidden // kpad) * kpad // 16, hidden, 16)
-        lead = {'fp16x2': (2,), 'fp32x3': (3,)}.get(plan, ())
+        self.convert, self.fmt = ar.operand, ar.fmt
+        s6 = (-(-k6 // ar.kpad) * ar.kpad // 16, rows6, 16)
+        s7 = (nb, -(-hidden // ar.kpad) * ar.kpad // 16, hidden, 16)
 
         def alloc(shape):
-            return torch.empty(lead + shape, device=device,
-                               dtype=torch.float16 if plan == 'fp16x2' else torch.bfloat16)
+            return torch.empty(ar.lead + shape, device=device, dtype=ar.dtype)
         self.scales = self.ovf = self.rm_table = self._bound = None
         # the SGD kernel can write the planes: a wave's 256 floats stay in one row, one pair of
         # hyper-parameters per matrix (otherwise: the element-wise kernel + re-split, no tables)
         writable = k6 % 256 == 0 and one_run6 and one_run7
-        if plan == 'fp16x2':
+        if ar.reports_maxima:
             self.scales = torch.zeros((4 * rows6,), device=device, dtype=torch.float32)
             self._arena = self.scales.view(2, 2, rows6)       # [operand][maxima | 1/scale][rows]
             self.operands = dict(
@@ -81,7 +79,7 @@ class FcPlanes(object):
         """ops.SgdPlaneRegions for an update launched on the arena from element `origin`: the
         fc6_w rows own6 = (r0, r1) (or None) are updated with their planes, the row ranges in
         `skip6` are left alone, fc7_w (with7) is updated whole."""
-        h2 = self.plan == 'fp16x2'
+        h2 = self.arith.reports_maxima
         p6, p7 = ((self.operands[k].planes if h2 else self.operands[k]) for k in ('w6', 'w7'))
         regs = [(self.o6 + r0 * self.k6 - origin, r1 - r0, self.k6,
                  self.rows6 if (r0, r1) == self.all6 else SKIP_ROWS, None, None, None, None)

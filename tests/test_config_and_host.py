@@ -845,3 +845,83 @@ def test_fc_planes_layout_and_region_tables(monkeypatch):
         with eng._timed(name, on=on):
             ran.append(name)
     assert len(ran) == 3 and not made
+
+
+def test_head_arith_views_are_the_engines_index_expressions(monkeypatch):
+    """naws_hip.head_arith at the sizes above: rows() / batches() of every plan's FcPlanes operands
+    are the very views the engine used to cut by hand (.rows / [:, :, r0:r1] / [:, r0:r1] and
+    .batches / [:, :nb] / [:nb]: same data_ptr, shape and strides, scales included), and the fp32
+    plan's lazy operands slice without a copy and reach ops.gemm with the trans_a / trans_b flags
+    of its five products."""
+    import torch
+    from naws_hip import head_arith, ops
+    from naws_hip.planes import FcPlanes
+    n6, k6, hid = 256, 256, 128
+    o6, total = 1024, 200000
+    ob = o6 + n6 * k6
+    o7 = ob + n6
+    ranges, batches = ((0, 256), (128, 256), (32, 96)), (1, 2)
+
+    def same(a, b):
+        assert (a.data_ptr(), tuple(a.shape), a.stride(), a.dtype) == \
+            (b.data_ptr(), tuple(b.shape), b.stride(), b.dtype)
+
+    by_hand = {'fp16x2': (lambda op, r0, r1: op.rows(r0, r1), lambda op, nb: op.batches(nb)),
+               'fp32x3': (lambda op, r0, r1: op[:, :, r0:r1], lambda op, nb: op[:, :nb]),
+               'bf16': (lambda op, r0, r1: op[:, r0:r1], lambda op, nb: op[:nb])}
+    for plan, (rows, bat) in by_hand.items():
+        ar = head_arith.plan(plan)
+        fc = FcPlanes(plan, n6, k6, hid, o6, ob, o7, total, torch.device('cpu'))
+        assert fc.arith is ar and head_arith.plan(ar) is ar and ar.planes16
+        cut = [(ar.rows(fc.operands['w6'], r0, r1), rows(fc.operands['w6'], r0, r1)) for r0, r1 in ranges]
+        cut += [(ar.batches(fc.operands[k], nb), bat(fc.operands[k], nb)) for k in ('w7', 'w7t') for nb in batches]
+        for got, want in cut:
+            assert type(got) is type(want)
+            if plan == 'fp16x2':
+                assert isinstance(got, ops.F16x2)
+                same(got.planes, want.planes)
+                same(got.scales, want.scales)
+                same(got.inv_scale, want.inv_scale)
+            else:
+                same(got, want)
+        for k in ('w6', 'w7', 'w7t'):           # an operand passes through; it is not re-split
+            assert ar.operand(fc.operands[k]) is fc.operands[k]
+    with pytest.raises(ValueError):
+        FcPlanes('fp32', n6, k6, hid, o6, ob, o7, total, torch.device('cpu'))
+    with pytest.raises(ValueError):
+        head_arith.plan('fp64')
+
+    # fp32: lazy (tensor, transposed) pairs
+    ar = head_arith.plan('fp32')
+    assert not ar.planes16 and not ar.reports_maxima and not ar.wgrad_update
+    t = torch.arange(40 * 256, dtype=torch.float32).view(40, 256)
+    w7 = torch.zeros((2, hid, hid))
+    n, tr = ar.operand(t), ar.operand(t, transpose=True)
+    assert n.x is t and tr.x is t and (n.t, tr.t) == (False, True) and ar.operand(n) is n
+    for r0, r1 in ranges:
+        a, b = ar.rows(n, r0, r1), ar.rows(tr, r0, r1)
+        same(a.x, t[r0:r1])
+        same(b.x, t[:, r0:r1])
+        assert (a.t, b.t) == (False, True)
+    for nb in batches:
+        same(ar.batches(ar.operand(w7), nb).x, w7[:nb])
+        same(ar.batches(ar.operand(w7, transpose=True), nb).x, w7[:nb])
+    calls = []
+    monkeypatch.setattr(ops, 'gemm', lambda a, b, trans_a=False, trans_b=False, out=None, **kw:
+                        calls.append((a, b, trans_a, trans_b, out, kw)))
+    x, w6 = torch.zeros((40, k6)), torch.zeros((n6, k6))
+    h6v, dz7v, dz6 = torch.zeros((2, 40, hid)), torch.zeros((2, 40, hid)), torch.zeros((40, n6))
+    out = torch.zeros(1)
+    products = [        # (A's operand, B's operand, the tensors and flags ops.gemm must see)
+        (ar.operand(x), ar.rows(ar.operand(w6), 0, 128), x, w6[:128], False, True),          # fc6 forward
+        (ar.operand(h6v), ar.batches(ar.operand(w7), 1), h6v, w7[:1], False, True),          # fc7 forward
+        (ar.operand(dz7v), ar.operand(w7, transpose=True), dz7v, w7, False, False),          # dZ6
+        (ar.rows(ar.operand(dz6, transpose=True), 32, 96), ar.operand(x, transpose=True),
+         dz6[:, 32:96], x, True, False),                                                     # dW6
+        (ar.operand(dz7v, transpose=True), ar.operand(h6v, transpose=True), dz7v, h6v, True, False)]  # dW7
+    for a, b, ta, tb, fa, fb in products:
+        ar.gemm_nt(a, b, out=out, alpha=2.0)
+        ga, gb, gfa, gfb, gout, kw = calls.pop()
+        same(ga, ta)
+        same(gb, tb)
+        assert (gfa, gfb) == (fa, fb) and gout is out and kw == dict(alpha=2.0) and not calls

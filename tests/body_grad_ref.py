@@ -1,11 +1,17 @@
 """Float64 references of the trainable conv body's backward (torch CPU double / numpy), shared by
-tests/test_gpu_body_backward.py:
+tests/test_gpu_body_backward.py, tests/test_gpu_body_backward_shapes.py and
+tests/test_body_backward_plan.py:
 
   conv_grads / conv_grads_wrong   Conv(+bias) gradients through torch autograd, and three
                                   deliberately wrong statements that the tests' bound must reject
+  WGRAD_CASES / wgrad_slices      the shapes that reach the weight gradient's split-K branches and
+                                  the slice count behind a workspace size
+  conv_case_int                   integer operands: every float32 sum exact, so the reference is
+                                  the answer bit for bit
   maxpool_select / maxpool_grad32 the element naws_maxpool2x2_nhwc_fwd selects (first of a, b, d, e
                                   equal to the maximum) and the float32 gather that adds the windows
                                   in ascending index - bit for bit what the kernel computes
+  pool_tie_input / tie_census     a feature map full of tied windows, and the count of them
   roi_pool_grad64                 float64 scatter through a given argmax, with the per-element
                                   number of contributions and sum of |terms| for the bound
   graph_grads64                   a recorded DetectionModelHelper graph restated in torch double:
@@ -50,7 +56,61 @@ def conv_grads_wrong(kind, x, w, b, dy, dilation):
     raise ValueError(kind)
 
 
+# The shapes of tests/test_gpu_body_backward_shapes.py: (N, H, W, Cin, Cout, dilation) -> the number
+# of K slices naws_conv3x3_nhwc_wgrad's plan takes there (tests/test_body_backward_plan.py holds the
+# library to it, so a change of the plan cannot quietly turn these back into one-slice cases).
+#   K = 1 (only the centre tap is non-zero) | H <= dilation | the smallest split, K = 518 / 556 (no
+#   multiple of 32) | a 64 + 32 residue in M and in N, 2 x 3 tiles, two images | slices limited by
+#   the tile count (8 x 8 tiles), the dgrad pack loops | the slice cap, the staging kernel loops,
+#   dgrad in the 64 x 128 x 16 conv form
+WGRAD_CASES = {
+    (1, 1, 1, 32, 32, 1): 1, (1, 1, 1, 32, 32, 2): 1,
+    (1, 2, 3, 32, 32, 2): 1,
+    (1, 20, 24, 64, 64, 1): 2, (1, 20, 24, 64, 64, 2): 2,
+    (2, 20, 24, 96, 160, 1): 4, (2, 20, 24, 96, 160, 2): 4,
+    (2, 28, 30, 512, 512, 1): 6,
+    (1, 100, 124, 512, 32, 1): 32,
+}
+
+
+def wgrad_slices(floats, case):
+    """The K slices behind naws_conv3x3_nhwc_wgrad_workspace_floats(*case) = the two staged
+    operands + the nine tap products + 3 partial planes per slice."""
+    n, h, w, cin, cout, d = case
+    rows = n * (h + 2 * d) * (w + 2 * d)
+    ks, rest = divmod(floats - rows * (cin + cout) - 9 * cin * cout, 3 * cin * cout)
+    assert rest == 0 and ks >= 1, (case, floats)
+    return ks
+
+
+def conv_case_int(case, seed, lo=-2, hi=2):
+    """x [N,Cin,H,W], w [Cout,Cin,3,3], dy [N,Cout,H,W]: integers lo..hi stored as float32.  Every
+    product and partial sum of the three gradients is then an integer below 2^24 (at most
+    4 N (H+2d) (W+2d) <= 4 * 12,852 for dW, 4 * 9 * 512 for dX), so float32 adds are exact in ANY
+    order and the float64 reference cast to float32 is the one right answer, bit for bit."""
+    n, h, w, cin, cout, _ = case
+    rng = np.random.default_rng(seed)
+    draw = lambda *s: rng.integers(lo, hi + 1, s).astype(np.float32)
+    return draw(n, cin, h, w), draw(cout, cin, 3, 3), draw(n, cout, h, w)
+
+
 # --------------------------------------------------------------------------------- max-pool ----
+def tie_census(x, stride):
+    """-> (t [4], s [4]) over the windows of x [N,H,W,C]: t[j] = windows in which element j (a, b, d,
+    e) equals the maximum together with at least one other element; s[j] = windows whose selected
+    element (the first at the maximum) is j."""
+    win = _windows(np.asarray(x, np.float32), stride)
+    top = win == win.max(axis=3, keepdims=True)
+    tied = top.sum(axis=3, keepdims=True) >= 2
+    return ((top & tied).sum(axis=(0, 1, 2, 4)),
+            np.bincount(np.argmax(top, axis=3).ravel(), minlength=4))
+
+
+def pool_tie_input(shape, stride):
+    """NHWC integers 0..3 as float32 (what a feature map looks like after ReLU: most windows tie)."""
+    return np.random.default_rng(31 + stride).integers(0, 4, shape).astype(np.float32)
+
+
 def _windows(x, stride):
     """x [N,H,W,C] -> [N,Ho,Wo,4,C] in the forward's order a = (y,x), b = (y,x+1), d, e."""
     n, h, w, c = x.shape

@@ -238,8 +238,13 @@ int naws_roi_iou_fwd(const float* rois, int R, float* J, void* stream);
  * `batch` independent problems with element strides strideA/B/C (bias and
  * aux stride by strideBias / strideC).  accumulate != 0 adds to C.
  * Dropout keep(m,n) is a counter-based hash of (seed, m*N+n); ratio in [0,1).
- * Alignment: every leading dimension and pointer offset must be a multiple
- * of 4 floats (16 B) -> NAWS_ERR_ARG otherwise. */
+ * Alignment: the OPERANDS are read with 16-byte loads: A, B, lda, ldb, strideA,
+ * strideB and each operand's contiguous extent (K, or M / N when stored
+ * transposed) must be multiples of 4 floats (16 B) -> NAWS_ERR_ARG otherwise.
+ * C and aux are stored / read one float at a time by the tile forms, so C, ldc,
+ * strideC, aux and ldaux may be ANY value >= N (an odd ldc is fine); only the
+ * short-K form (no transposes, K <= 64) needs them 16-byte aligned, and the
+ * entry falls back to the tile form when they are not - the same values. */
 int naws_gemm_f32(int transA, int transB, int M, int N, int K,
                   const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                   int batch, int64_t strideA, int64_t strideB, int64_t strideC,

@@ -32,6 +32,19 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _workspace(workspace, need, device, sizer, dtype=_f32):
+    """A kernel's scratch of `need` elements (what the library's `sizer` declares): allocated when
+    None; a caller's own must be contiguous, of `dtype` and at least that long (the contract of
+    conv3x3_nhwc_wgrad's workspace)."""
+    if workspace is None:
+        return torch.empty((max(int(need), 4),), device=device, dtype=dtype)
+    if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda
+            or workspace.dtype != dtype or workspace.numel() < need
+            or not workspace.is_contiguous()):
+        raise TypeError('workspace: contiguous %s on the device, >= %s' % (dtype, sizer))
+    return workspace
+
+
 # ----------------------------------------------------------------------------
 # conv body
 # ----------------------------------------------------------------------------
@@ -81,13 +94,13 @@ def winograd4_weight_transform(w_oihw):
     return u
 
 
-def conv3x3_winograd_nhwc(x, u, bias, dilation=1, relu=True, out=None):
+def conv3x3_winograd_nhwc(x, u, bias, dilation=1, relu=True, out=None, workspace=None):
     _chk(x, 'x'); _chk(u, 'U')
     n, h, w, cin = x.shape
     cout = u.shape[1]
     y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
     nws = L.load().naws_winograd_workspace_floats(n, h, w, cin, cout, dilation)
-    ws = torch.empty((nws,), device=x.device, dtype=_f32)
+    ws = _workspace(workspace, nws, x.device, 'naws_winograd_workspace_floats')
     L.call('naws_conv3x3_winograd_nhwc_fwd', x.data_ptr(), u.data_ptr(), _ptr(bias), n, h, w, cin,
            cout, dilation, int(relu), ws.data_ptr(), y.data_ptr(), _stream())
     return y
@@ -168,7 +181,7 @@ def conv3x3_nhwc_wgrad(x, dy, dilation=1, workspace=None):
 # RoI ops
 # ----------------------------------------------------------------------------
 def roi_pool_f(x, rois, pooled_h=7, pooled_w=7, spatial_scale=0.125, boost=None,
-               layout='NCHW', with_argmax=False, out=None, hier=False):
+               layout='NCHW', with_argmax=False, out=None, hier=False, workspace=None):
     _chk(x, 'x'); _chk(rois, 'rois')
     if rois.dim() != 2 or rois.shape[1] != 5:
         raise L.NawsError('naws_roi_pool_f_fwd', L.ERR_SHAPE)
@@ -188,8 +201,8 @@ def roi_pool_f(x, rois, pooled_h=7, pooled_w=7, spatial_scale=0.125, boost=None,
                                                 dtype=_f32)
     if hier and layout == 'NHWC' and not with_argmax and c % 64 == 0 and r > 0:
         # bin maxima over precomputed 2x2 / 4x4 block maxima: same values, ~8x less gather
-        ws = torch.empty((L.load().naws_roi_pool_workspace_floats(n, c, h, w),), device=x.device,
-                         dtype=_f32)
+        ws = _workspace(workspace, L.load().naws_roi_pool_workspace_floats(n, c, h, w), x.device,
+                        'naws_roi_pool_workspace_floats')
         L.call('naws_roi_pool_f_nhwc_hier_fwd', x.data_ptr(), n, c, h, w, rois.data_ptr(), r,
                _ptr(boost), pooled_h, pooled_w, float(spatial_scale), ws.data_ptr(), y.data_ptr(),
                _stream())
@@ -304,7 +317,7 @@ def roi_pool_f_f16x2_range(x, rois, amax_words, out, r0, r1, maps, pooled_h=7, p
 
 
 def roi_pool_f_f16x2(x, rois, amax_words, pooled_h=7, pooled_w=7, spatial_scale=0.125, boost=None,
-                     hier=True, maps=None):
+                     hier=True, maps=None, workspace=None):
     """RoIPoolF (+ boost) on NHWC features, written directly as the fp16x2 operand of the fc6
     GEMM: F16x2 with planes [2, K/16, R, 16], K = C*ph*pw, scaled per roi from the bound
     max|x| of the roi's image (`amax_words`: int32 [n] bit patterns) * |boost|."""
@@ -332,8 +345,8 @@ def roi_pool_f_f16x2(x, rois, amax_words, pooled_h=7, pooled_w=7, spatial_scale=
                out.scales.data_ptr(), _stream())
         return out
     if hier:
-        ws = torch.empty((L.load().naws_roi_pool_workspace_floats(n, c, h, w),), device=x.device,
-                         dtype=_f32)
+        ws = _workspace(workspace, L.load().naws_roi_pool_workspace_floats(n, c, h, w), x.device,
+                        'naws_roi_pool_workspace_floats')
         L.call('naws_roi_pool_f_f16x2_hier_fwd', x.data_ptr(), n, c, h, w, rois.data_ptr(), r,
                _ptr(boost), pooled_h, pooled_w, float(spatial_scale), amax_words.data_ptr(),
                amax_words.numel(), ws.data_ptr(), out.planes.data_ptr(), out.scales.data_ptr(),
@@ -369,7 +382,7 @@ def roi_pool_f_bf16_slab(x, rois, maps, pooled_h=7, pooled_w=7, spatial_scale=0.
     return out
 
 
-def bf16_slab_transpose(p):
+def bf16_slab_transpose(p, out=None):
     """bf16 slab operand [K/16, R, 16] -> [Rpad/16, K, 16] (Rpad = R rounded up to 64, rows >= R
     zero): the same matrix with the other index K-contiguous (to_bf16_slab(x, transpose=True) of
     the matrix the slab was rounded from)."""
@@ -378,12 +391,15 @@ def bf16_slab_transpose(p):
         raise TypeError('p must be a contiguous bf16 slab tensor [K/16, R, 16]')
     k, r = p.shape[0] * 16, p.shape[1]
     rp = (r + 63) // 64 * 64
-    q = torch.empty((rp // 16, k, 16), device=p.device, dtype=torch.bfloat16)
+    q = out if out is not None else torch.empty((rp // 16, k, 16), device=p.device,
+                                                dtype=torch.bfloat16)
+    if tuple(q.shape) != (rp // 16, k, 16) or q.dtype != torch.bfloat16 or not q.is_contiguous():
+        raise TypeError('out must be a contiguous bf16 [Rpad/16, K, 16] tensor')
     L.call('naws_bf16_slab_transpose', p.data_ptr(), r, k, rp, q.data_ptr(), _stream())
     return q
 
 
-def f16_planes_transpose(op):
+def f16_planes_transpose(op, out=None):
     """F16x2 with planes [2, K/16, R, 16] -> F16x2 with planes [2, Rpad/16, K, 16] holding the same
     scaled matrix K(=rows)-contiguous (Rpad = R rounded up to 32, zero rows) and scales of ones:
     the B operand of dW = dY^T X when dY is split with kmul = op.inv_scale."""
@@ -392,7 +408,10 @@ def f16_planes_transpose(op):
         raise TypeError('expects contiguous unbatched f16 planes [2, K/16, R, 16]')
     k, r = p.shape[1] * 16, p.shape[2]
     rpad = (r + 31) // 32 * 32
-    q = torch.empty((2, rpad // 16, k, 16), device=p.device, dtype=torch.float16)
+    q = out if out is not None else torch.empty((2, rpad // 16, k, 16), device=p.device,
+                                                dtype=torch.float16)
+    if tuple(q.shape) != (2, rpad // 16, k, 16) or q.dtype != torch.float16 or not q.is_contiguous():
+        raise TypeError('out must be contiguous f16 planes [2, Rpad/16, K, 16]')
     L.call('naws_f16_planes_transpose', p.data_ptr(), r, k, rpad, q.data_ptr(), _stream())
     return F16x2(q, torch.ones((2, k), device=p.device, dtype=_f32))
 
@@ -442,6 +461,13 @@ def _amax_args(rowmax, rowmax_seg, colmax, colmax_rowmul):
     return (_ptr(rowmax), int(rowmax_seg), _ptr(colmax), _ptr(colmax_rowmul))
 
 
+def _chk_batched_aux(fn, aux, out, batch):
+    """The GEMM kernels step a batched aux by the OUTPUT's batch stride (include/naws.h: "aux
+    stride by strideC"): a batched call takes a 3-D aux whose batch stride equals out's."""
+    if aux is not None and batch > 1 and (aux.dim() != 3 or aux.stride(0) != out.stride(0)):
+        raise L.NawsError(fn, L.ERR_ARG)
+
+
 def gemm(a, b, trans_a=False, trans_b=False, out=None, epilogue=L.EPI_NONE, bias=None, aux=None,
          alpha=1.0, drop_ratio=0.0, seed=0, accumulate=False, rowmax=None, rowmax_seg=0,
          colmax=None, colmax_rowmul=None):
@@ -473,6 +499,7 @@ def gemm(a, b, trans_a=False, trans_b=False, out=None, epilogue=L.EPI_NONE, bias
     sbias = 0
     if bias is not None and bias.dim() == 2:
         sbias = bias.stride(0)
+    _chk_batched_aux('naws_gemm_f32_amax', aux, out, batch)
     L.call('naws_gemm_f32_amax', int(trans_a), int(trans_b), m, n, k, a.data_ptr(), a2.stride(0),
            b.data_ptr(), b2.stride(0), out.data_ptr(), c2.stride(0), batch, sa, sb, sc,
            epilogue, _ptr(bias), sbias, _ptr(aux),
@@ -537,6 +564,7 @@ def gemm_bf16_nt(a, b, out=None, epilogue=L.EPI_NONE, bias=None, aux=None, alpha
         out = torch.empty(((batch, m, n) if batched else (m, n)), device=a.device, dtype=_f32)
     c2 = out[0] if batched else out
     sbias = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
+    _chk_batched_aux('naws_gemm_bf16_nt', aux, out, batch)
     L.call('naws_gemm_bf16_nt', m, n, k, a.data_ptr(), int(a.dtype == torch.bfloat16),
            a2.stride(0), b.data_ptr(), int(b.dtype == torch.bfloat16), b2.stride(0),
            out.data_ptr(), c2.stride(0), batch, (a.stride(0) if batched else 0),
@@ -623,7 +651,10 @@ def conv3x3_nhwc_f32x3(x, w3, bias, dilation=1, relu=True, out=None, pool2=False
     if w3.dtype != torch.bfloat16 or w3.shape[0] != 3 or w3.shape[1] * 16 != 9 * cin:
         raise TypeError('w3 must be the bf16 planes [3, 9*Cin/16, Cout, 16] of the packed weight')
     if pool2:
-        y = torch.empty((n, h // 2, w // 2, cout), device=x.device, dtype=_f32)
+        shape = (n, h // 2, w // 2, cout)
+        y = out if out is not None else torch.empty(shape, device=x.device, dtype=_f32)
+        if tuple(y.shape) != shape or y.dtype != _f32 or not y.is_contiguous():
+            raise TypeError('out must be a contiguous fp32 %s tensor' % (shape,))
         L.call('naws_conv3x3_nhwc_f32x3_pool_fwd', x.data_ptr(), w3.data_ptr(), _ptr(bias), n, h, w,
                cin, cout, int(relu), y.data_ptr(), _stream())
         return y
@@ -633,7 +664,7 @@ def conv3x3_nhwc_f32x3(x, w3, bias, dilation=1, relu=True, out=None, pool2=False
     return y
 
 
-def conv3x3_winograd_nhwc_f32x3(x, u3, bias, dilation=1, relu=True, out=None):
+def conv3x3_winograd_nhwc_f32x3(x, u3, bias, dilation=1, relu=True, out=None, workspace=None):
     """Winograd F(2x2,3x3) with fp32x3 GEMMs; u3 = split_bf16x3(winograd_weight_transform(w))
     = planes [3, 16, Cin/16, Cout, 16]."""
     _chk(x, 'x')
@@ -643,7 +674,7 @@ def conv3x3_winograd_nhwc_f32x3(x, u3, bias, dilation=1, relu=True, out=None):
         raise TypeError('u3 must be the bf16 planes [3, 16, Cin/16, Cout, 16] of U')
     y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
     nws = L.load().naws_winograd_f32x3_workspace_floats(n, h, w, cin, cout, dilation)
-    ws = torch.empty((nws,), device=x.device, dtype=_f32)
+    ws = _workspace(workspace, nws, x.device, 'naws_winograd_f32x3_workspace_floats')
     L.call('naws_conv3x3_winograd_nhwc_f32x3_fwd', x.data_ptr(), u3.data_ptr(), _ptr(bias), n, h,
            w, cin, cout, dilation, int(relu), ws.data_ptr(), y.data_ptr(), _stream())
     return y
@@ -703,7 +734,7 @@ def winograd_weight_columns(u):
 
 
 def conv3x3_winograd_nhwc_f16x2(x, u2, bias, dilation=1, relu=True, out=None, amax_in=None,
-                                amax_out=None):
+                                amax_out=None, workspace=None):
     """Winograd F(2x2,3x3) with fp16x2 GEMMs; u2 = split_f16x2(winograd_weight_transform(w))
     (F16x2: planes [2, 16, Cin/16, Cout, 16], scales [2, 16, Cout]) - or F(4x4,3x3) when u2 =
     split_f16x2(winograd4_weight_transform(w)) (planes [2, 36, Cin/16, Cout, 16]).  amax_in / amax_out: optional
@@ -719,7 +750,7 @@ def conv3x3_winograd_nhwc_f16x2(x, u2, bias, dilation=1, relu=True, out=None, am
     y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
     if tuple(u2.planes.shape[:3]) == (2, 36, cin // 16):          # winograd4_weight_transform
         nws = L.load().naws_winograd4_f16x2_workspace_floats(n, h, w, cin, cout, dilation)
-        ws = torch.empty((nws,), device=x.device, dtype=_f32)
+        ws = _workspace(workspace, nws, x.device, 'naws_winograd4_f16x2_workspace_floats')
         if amax_in is None:
             amax_in = amax_word(x)
         L.call('naws_conv3x3_winograd4_nhwc_f16x2_fwd', x.data_ptr(), u2.planes.data_ptr(),
@@ -727,7 +758,7 @@ def conv3x3_winograd_nhwc_f16x2(x, u2, bias, dilation=1, relu=True, out=None, am
                ws.data_ptr(), y.data_ptr(), _ptr(amax_in), _ptr(amax_out), _stream())
         return y
     nws = L.load().naws_winograd_f16x2_workspace_floats(n, h, w, cin, cout, dilation)
-    ws = torch.empty((nws,), device=x.device, dtype=_f32)
+    ws = _workspace(workspace, nws, x.device, 'naws_winograd_f16x2_workspace_floats')
     if col and not hasattr(L.load(), 'naws_conv3x3_winograd_nhwc_f16x2_col_fwd'):
         raise RuntimeError('the frequency-column Winograd form lives in the A/B build only '
                            '(make -C na-fwebsod_amd/csrc AB=1; NAWS_LIB=.../libnaws_hip_ab.so): it '
@@ -761,7 +792,7 @@ def soft_nms_per_class(dets, counts, sigma, overlap_thresh, score_thresh, method
     return out, keep, oc
 
 
-def nms_per_class(boxes, scores, score_thresh, nms_thresh):
+def nms_per_class(boxes, scores, score_thresh, nms_thresh, workspace=None):
     """Per-class greedy NMS of one image on the GPU (cython_nms.pyx `nms` semantics).
     boxes [R,4] (or [R,4*C] class-tiled, the reference's pred_boxes), scores [R,C] (fg classes).
     -> keep [C,R] bool: box r survives for class c (score > score_thresh and not suppressed).
@@ -782,7 +813,10 @@ def nms_per_class(boxes, scores, score_thresh, nms_thresh):
         off = b3.shape[1] - c                                     # skip the background column(s)
         sb = b3[order, (torch.arange(c, device=dev) + off)[:, None]]
     sb = sb.to(_f32).contiguous()
-    ws = torch.empty((L.load().naws_nms_workspace_bytes(c, r) // 8,), dtype=torch.int64, device=dev)
+    # (workspace: int32 words covering naws_nms_workspace_bytes; the kernel's 64-bit masks need it
+    # 8-byte aligned, which the entry checks)
+    ws = _workspace(workspace, (L.load().naws_nms_workspace_bytes(c, r) + 3) // 4, dev,
+                    'naws_nms_workspace_bytes / 4', torch.int32)
     keep_sorted = torch.empty((c, r), dtype=torch.int32, device=dev)
     L.call('naws_nms_sorted_fwd', sb.data_ptr(), counts.data_ptr(), c, r, float(nms_thresh),
            ws.data_ptr(), keep_sorted.data_ptr(), _stream())
@@ -870,6 +904,7 @@ def gemm_bf16_slab_nt(a, b, out=None, epilogue=L.EPI_NONE, bias=None, aux=None, 
         out = torch.empty(((batch, mm, nn) if batched else (mm, nn)), device=a.device, dtype=_f32)
     c2 = out[0] if batched else out
     sbias = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
+    _chk_batched_aux('naws_gemm_bf16_slab_nt', aux, out, batch)
     L.call('naws_gemm_bf16_slab_nt', mm, nn, k, a.data_ptr(), a.stride(-3), b.data_ptr(),
            b.stride(-3), out.data_ptr(), c2.stride(0), batch, (a.stride(0) if batched else 0),
            (b.stride(0) if batched else 0), (out.stride(0) if batched else 0), epilogue,
@@ -904,6 +939,7 @@ def gemm_f32x3_nt(a3, b3, out=None, epilogue=L.EPI_NONE, bias=None, aux=None, al
         out = torch.empty(((batch, mm, nn) if batched else (mm, nn)), device=a3.device, dtype=_f32)
     c2 = out[0] if batched else out
     sbias = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
+    _chk_batched_aux('naws_gemm_f32x3_nt', aux, out, batch)
     L.call('naws_gemm_f32x3_nt', mm, nn, k, a3.data_ptr(), a3.stride(-3), a3.stride(0),
            b3.data_ptr(), b3.stride(-3), b3.stride(0), out.data_ptr(), c2.stride(0), batch,
            (a3.stride(1) if batched else 0), (b3.stride(1) if batched else 0),
@@ -984,6 +1020,7 @@ def gemm_f32_f16x2_nt(a, b, out=None, epilogue=L.EPI_NONE, bias=None, aux=None, 
         out = torch.empty(((batch, mm, nn) if batched else (mm, nn)), device=a3.device, dtype=_f32)
     c2 = out[0] if batched else out
     sbias = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
+    _chk_batched_aux('naws_gemm_f32_f16x2_nt_amax', aux, out, batch)
     L.call('naws_gemm_f32_f16x2_nt_amax', mm, nn, k, a3.data_ptr(), a3.stride(-3), a3.stride(0),
            sa.data_ptr(), b3.data_ptr(), b3.stride(-3), b3.stride(0), sb.data_ptr(),
            out.data_ptr(), c2.stride(0), batch,
@@ -1221,7 +1258,7 @@ def wsddn_outputs_grad(alpha_cls, alpha_det, rois_pred, cls_prob, d_cls_prob, se
     return out
 
 
-def entropy_gate(rois, rois_pred, cls_prob, labels_oh, seg_off, max_seg_len):
+def entropy_gate(rois, rois_pred, cls_prob, labels_oh, seg_off, max_seg_len, workspace=None):
     """-> class_weight, class_weight_noise, hatE_sum, hatE_sum_norm, each [nseg,C]."""
     _chk(rois, 'rois'); _chk(rois_pred, 'rois_pred'); _chk(cls_prob, 'cls_prob')
     _chk(labels_oh, 'labels_oh')
@@ -1229,7 +1266,7 @@ def entropy_gate(rois, rois_pred, cls_prob, labels_oh, seg_off, max_seg_len):
     nseg = seg_off.numel() - 1
     dev = rois.device
     nws = L.load().naws_entropy_gate_workspace_floats(rt, c, nseg, max_seg_len)
-    ws = torch.empty((max(nws, 1),), device=dev, dtype=_f32)
+    ws = _workspace(workspace, nws, dev, 'naws_entropy_gate_workspace_floats')
     # one buffer: [class_weight | class_weight_noise] is then the [2, nseg, C] weight operand of the
     # two branches' cross entropy as it stands (no stack)
     buf = torch.empty((4, nseg, c), device=dev, dtype=_f32)
@@ -1417,7 +1454,7 @@ def split_f16x2_row_range_if(x, rowmax, out, row0, row1, cond=None, cond_value=0
 # OICR refinement operators
 # ----------------------------------------------------------------------------
 def roi_label(s, u, l, cw=None, fg_thresh=0.5, bg_thresh_hi=0.5, bg_thresh_lo=-1.0, top_k=1,
-              num_pos=9999, num_neg=9999, stats=None):
+              num_pos=9999, num_neg=9999, stats=None, workspace=None):
     """-> (RL int32 [n], RW fp32 [n]); stats (fp32 [4], optional) accumulates the op's counters."""
     _chk(s, 'S'); _chk(u, 'U'); _chk(l, 'L')
     if s.dim() != 2 or u.dim() != 2 or l.dim() != 2 or l.shape[0] != 1 or \
@@ -1428,8 +1465,8 @@ def roi_label(s, u, l, cw=None, fg_thresh=0.5, bg_thresh_hi=0.5, bg_thresh_lo=-1
     if cw is not None:
         _chk(cw, 'CW')
     dev = s.device
-    ws = torch.empty((max(L.load().naws_roi_label_workspace_bytes(n, c, top_k), 16) // 4,),
-                     device=dev, dtype=torch.int32)
+    ws = _workspace(workspace, (L.load().naws_roi_label_workspace_bytes(n, c, top_k) + 3) // 4, dev,
+                    'naws_roi_label_workspace_bytes / 4', torch.int32)
     rl = torch.empty((n,), device=dev, dtype=torch.int32)
     rw = torch.empty((n,), device=dev, dtype=_f32)
     st = stats if stats is not None else torch.zeros((4,), device=dev, dtype=_f32)
@@ -1439,7 +1476,7 @@ def roi_label(s, u, l, cw=None, fg_thresh=0.5, bg_thresh_hi=0.5, bg_thresh_lo=-1
     return rl, rw
 
 
-def softmax_with_loss_n(x, t, w=None, scale=1.0):
+def softmax_with_loss_n(x, t, w=None, scale=1.0, workspace=None):
     """-> (P [N,D], loss [1])."""
     _chk(x, 'X'); _chk(t, 'T', torch.int32)
     if x.dim() != 2 or t.numel() != x.shape[0] or (w is not None and w.numel() != x.shape[0]):
@@ -1447,8 +1484,8 @@ def softmax_with_loss_n(x, t, w=None, scale=1.0):
     if w is not None:
         _chk(w, 'W')
     n, d = x.shape
-    ws = torch.empty((L.load().naws_softmax_with_loss_n_workspace_floats(n),), device=x.device,
-                     dtype=_f32)
+    ws = _workspace(workspace, L.load().naws_softmax_with_loss_n_workspace_floats(n), x.device,
+                    'naws_softmax_with_loss_n_workspace_floats')
     p = torch.empty_like(x)
     loss = torch.empty((1,), device=x.device, dtype=_f32)
     L.call('naws_softmax_with_loss_n_fwd', x.data_ptr(), t.data_ptr(), _ptr(w), n, d, float(scale),
@@ -1456,13 +1493,13 @@ def softmax_with_loss_n(x, t, w=None, scale=1.0):
     return p, loss
 
 
-def softmax_with_loss_n_grad(t, w, p, dloss, scale=1.0):
+def softmax_with_loss_n_grad(t, w, p, dloss, scale=1.0, workspace=None):
     _chk(p, 'P'); _chk(t, 'T', torch.int32); _chk(dloss, 'd_avg_loss')
     if w is not None:
         _chk(w, 'W')
     n, d = p.shape
-    ws = torch.empty((L.load().naws_softmax_with_loss_n_workspace_floats(n),), device=p.device,
-                     dtype=_f32)
+    ws = _workspace(workspace, L.load().naws_softmax_with_loss_n_workspace_floats(n), p.device,
+                    'naws_softmax_with_loss_n_workspace_floats')
     dx = torch.empty_like(p)
     L.call('naws_softmax_with_loss_n_bwd', t.data_ptr(), _ptr(w), p.data_ptr(), dloss.data_ptr(), n,
            d, float(scale), ws.data_ptr(), dx.data_ptr(), _stream())

@@ -176,6 +176,60 @@ int naws_roi_pool_f_bwd(const float* dY, const int32_t* argmax, const float* roi
                         float* dX, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * a-2b  RoIAlign / RoIAlignGradient (FAST_RCNN.ROI_XFORM_METHOD RoIAlign)
+ *   ref: detectron/modeling/detector.py:268-331 (op emission, sampling_ratio =
+ *        FAST_RCNN.ROI_XFORM_SAMPLING_RATIO); the operator is Caffe2's built-in
+ *        (pytorch v1.3.0 caffe2/operators/roi_align_op.cc and
+ *        roi_align_gradient_op.cu, aligned = false).  It is vendored neither in
+ *        the reference tree nor on the build machine: parity with a
+ *        reference-executed number is UNPINNED, the arithmetic below is the
+ *        contract.
+ * X: NHWC [N,H,W,C].  rois: [R,5] = (batch_idx, x1, y1, x2, y2) in image
+ * pixels.  Y: [R,C,ph,pw]; no argmax.  Geometry, every operation ONE fp32
+ * operation rounded on its own (no FMA), s = spatial_scale:
+ *   xs = x1*s  ys = y1*s  xe = x2*s  ye = y2*s          (coordinates are not rounded)
+ *   rw = max(xe - xs, 1)   rh = max(ye - ys, 1)   bw = rw / pw   bh = rh / ph
+ *   gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / pw)   (gh from rh, ph)
+ *   sample (p, i) of the row axis, p < ph, i < gh:
+ *     y = (ys + p*bh) + ((i + 0.5f) * bh) / gh
+ *     valid iff y >= -1 && y <= H  (a NaN is invalid);  if (y <= 0) y = 0;  lo = (int)y;
+ *     if (lo >= H-1) { hi = lo = H-1; y = lo; } else hi = lo + 1;     l = y - lo
+ *   columns likewise with xs, bw, gw, W.
+ * Values (any order, with or without FMA): with h = 1 - l a sample pair adds
+ *   hy*hx*X[lo_y,lo_x] + hy*lx*X[lo_y,hi_x] + ly*hx*X[hi_y,lo_x] + ly*lx*X[hi_y,hi_x]
+ * if both axes are valid, else 0; a bin is the sum over its gh*gw pairs divided
+ * by gh*gw (invalid pairs count in the divisor).  The kernels evaluate the
+ * separable form Y[c,p,q] = sum_h sum_w Ay[p,h] Ax[q,w] X[h,w,c], Ay[p,h] = the
+ * summed row weights of bin p on row h divided by gh; a pixel whose summed
+ * weight is 0 is not read.  The forward adds in a fixed order: Y is
+ * bit-reproducible.  The backward is the exact transpose,
+ *   dX[b, tap] += dY[r,c,p,q] * weight / (gh*gw),
+ * one no-return float atomic add (global_atomic_add_f32) per (roi, weighted
+ * pixel, channel): rois that share a pixel add in no fixed order, so dX is
+ * reproducible to rounding, not to the bit.  dX is zero-filled by the entry
+ * (also when R == 0) and stays exactly 0 wherever no valid sample has a tap.
+ * Defined where the reference loop has no checks at all (deviations):
+ *   - a roi with a non-finite scaled coordinate is invalid as a whole: its Y is
+ *     0 and it adds no gradient;
+ *   - so is a roi whose batch index (int)rois[r,0] is outside [0,N) (or NaN);
+ *   - so is a roi whose ADAPTIVE gh or gw exceeds 1024 (a side above 7168
+ *     feature pixels at 7x7).
+ * No X element outside the blob is read and every loop is bounded (by ph, pw,
+ * H, W, sampling_ratio or 1024), whatever the rois hold.  Any C > 0: the lanes
+ * of a 64-channel tile that run past C are masked.
+ * Errors, all before any launch: R<0, N/C/H/W/ph/pw<=0 -> SHAPE;
+ * sampling_ratio<0 or spatial_scale not > 0 -> ARG; a missing pointer -> NULL;
+ * pooled_h*pooled_w (with the ph*H + pw*W weight tables) beyond the LDS
+ * staging -> UNSUPPORTED.
+ * ------------------------------------------------------------------------ */
+int naws_roi_align_fwd(const float* X, int N, int C, int H, int W, const float* rois, int R,
+                       int pooled_h, int pooled_w, float spatial_scale, int sampling_ratio,
+                       float* Y, void* stream);
+int naws_roi_align_bwd(const float* dY, const float* rois, int R, int N, int C, int H, int W,
+                       int pooled_h, int pooled_w, float spatial_scale, int sampling_ratio,
+                       float* dX, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * RoIContext / RoILoopPool: the contextual WSDDN head (WSL.CONTEXT)
  *   ref: detectron/modeling/wsl_heads.py:684-766 (op emission),
  *        detectron/ops/roi_context_op.cu, detectron/ops/roi_loop_pool_op.cu.

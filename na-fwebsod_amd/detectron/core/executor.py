@@ -74,6 +74,8 @@ class NetExecutor(object):
                     # the canonical list is built under the current cfg, so it contains CenterLoss
                     # too: the fused engine does not compute that loss and must not be chosen
                     not cfg.WSL.CENTER_LOSS and
+                    # likewise RoIAlign: the engine pools with RoIPoolF whatever the op list says
+                    cfg.FAST_RCNN.ROI_XFORM_METHOD == 'RoIPoolF' and
                     sig == canonical_na_wsddn_signature(model.train, model.num_classes))
         self.plan = 'fused' if fused_ok else 'interpreted'
         self.engine = None
@@ -241,6 +243,9 @@ class NetExecutor(object):
         elif t == 'RoIPoolF':
             ws[out[0]], ws[out[1]] = O.RoIPoolF(x[0], x[1], a['pooled_h'], a['pooled_w'],
                                                 a['spatial_scale'])
+        elif t == 'RoIAlign':
+            ws[out[0]] = O.RoIAlign(x[0], x[1], a['pooled_h'], a['pooled_w'], a['spatial_scale'],
+                                    a.get('sampling_ratio', 0))
         elif t == 'RoIContext':      # inputs (rois, data): the clamp bounds are the image blob's dims
             ws[out[0]], ws[out[1]] = O.RoIContext(x[0], ws['data'],
                                                   context_ratio=a.get('context_ratio', 1.8))
@@ -363,6 +368,9 @@ class NetExecutor(object):
                                      pad=a['pad'], stride=a['stride'])]
         elif t == 'RoIPoolF':      # outputs Y, argmax: the forward's own selection
             res = [O.RoIPoolFGradient(ws[ins[0]], ws[ins[1]], ws[outs[1]], gout[0]), None]
+        elif t == 'RoIAlign':      # one output: the geometry is rebuilt from the rois
+            res = [O.RoIAlignGradient(ws[ins[0]], ws[ins[1]], gout[0], a['pooled_h'], a['pooled_w'],
+                                      a['spatial_scale'], a.get('sampling_ratio', 0)), None]
         elif t == 'Relu':
             res = [O.ReluGradient(ws[outs[0]], gout[0])]
         elif t == 'Dropout':

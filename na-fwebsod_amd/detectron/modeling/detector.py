@@ -53,7 +53,7 @@ _GRAD_INPUTS = {
     'RoIFeatureBoost': (0,), 'MinEntropyLoss': (0,), 'SoftmaxWithLossN': (0,),
     'CenterLoss': (2,),     # the features only (center_loss_op.cc:55-58): the centres update themselves
     # the trainable conv body (TRAIN.FREEZE_CONV_BODY False): features only for the two poolings
-    'Conv': (0, 1, 2), 'MaxPool': (0,), 'RoIPoolF': (0,),
+    'Conv': (0, 1, 2), 'MaxPool': (0,), 'RoIPoolF': (0,), 'RoIAlign': (0,),
 }
 _NO_GRAD = {'StopGradient', 'RoIIoU', 'Stat', 'Accuracy', 'ConstantFill', 'Shape', 'Cast',
             'DequeueBlobs', 'RoILabel', 'RoIEntropy', 'BoxWithNMSLimit', 'RoIContext'}
@@ -154,12 +154,16 @@ class DetectionModelHelper(object):
     def RoIFeatureTransform(self, blobs_in, blob_out, blob_rois='rois', method='RoIPoolF',
                             resolution=7, spatial_scale=1. / 16., sampling_ratio=0):
         """Single feature level only (FPN is outside the hot path).  ref: detector.py:268-331."""
-        assert method in {'RoIPoolF', 'RoILoopPool'}, 'Unknown pooling method: {}'.format(method)
+        assert method in {'RoIPoolF', 'RoILoopPool', 'RoIAlign'}, \
+            'Unknown pooling method: {}'.format(method)
         assert not isinstance(blobs_in, list), 'FPN RoI transforms are not on the hot path'
-        out = self.net.add(method, [blobs_in, blob_rois], [blob_out, '_argmax_' + blob_out],
+        # the two max poolings carry an argmax blob, RoIAlign has one output (ref :287, :321)
+        has_argmax = method in {'RoIPoolF', 'RoILoopPool'}
+        out = self.net.add(method, [blobs_in, blob_rois],
+                           [blob_out] + (['_argmax_' + blob_out] if has_argmax else []),
                            dict(pooled_w=resolution, pooled_h=resolution,
                                 spatial_scale=spatial_scale, sampling_ratio=sampling_ratio))
-        return out[0]
+        return out[0] if has_argmax else out
 
     # ---------------------------------------------------------- losses / metrics
     def AddLosses(self, losses):

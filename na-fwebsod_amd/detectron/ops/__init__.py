@@ -16,7 +16,7 @@ Custom ops (reference detectron/ops/*):
   CenterLoss(+Gradient)                   center_loss_op.cu:33-568        (WSL.CENTER_LOSS)
   ACMWeightDecayMomentumSGDUpdate         acm_weightdecay_momentum_sgd_op.h:48-112
 Caffe2 built-ins used by the path (pytorch v1.3.0 caffe2/operators, restated): RoIPoolF
-(+Gradient), Conv(+Gradient), Relu, MaxPool(+Gradient), FC, Dropout, Softmax, Transpose,
+(+Gradient), RoIAlign(+Gradient), Conv(+Gradient), Relu, MaxPool(+Gradient), FC, Dropout, Softmax, Transpose,
 Add/Sub/Mul/Div (numpy-style broadcast), ReduceSum, Log, Scale, ReplaceNaN, MatMul, LeakyRelu, Clip, ConstantFill,
 Shape/Cast (host), AveragedLoss, Accuracy, StopGradient, Concat/Split (views).
 
@@ -44,6 +44,22 @@ def RoIPoolF(X, R, pooled_h=1, pooled_w=1, spatial_scale=1.0, sampling_ratio=0):
 def RoIPoolFGradient(X, R, argmax, dY):
     """-> dX (X's shape): dX[b, c, argmax] += dY[r, c, ph, pw]; empty bins (argmax -1) add nothing."""
     return _k.roi_pool_f_grad(dY.contiguous(), argmax, R, tuple(X.shape), layout='NCHW')
+
+
+def RoIAlign(X, R, pooled_h=1, pooled_w=1, spatial_scale=1.0, sampling_ratio=0):
+    """-> Y [n,C,ph,pw] (no argmax): the average of sampling_ratio^2 bilinear samples per bin
+    (0: ceil(roi side / bins) per axis), roi coordinates not rounded (aligned = false).  The
+    arithmetic is stated in include/naws.h (a-2b); Caffe2's own operator was never executed
+    against it."""
+    return _k.roi_align(X, R, pooled_h, pooled_w, spatial_scale, sampling_ratio, layout='NCHW')
+
+
+def RoIAlignGradient(X, R, dY, pooled_h=1, pooled_w=1, spatial_scale=1.0, sampling_ratio=0):
+    """-> dX (X's shape), the exact transpose of RoIAlign: every tap gets dY * weight / (gh*gw)."""
+    if tuple(dY.shape[2:]) != (pooled_h, pooled_w):
+        raise NawsError('RoIAlignGradient', _L.ERR_SHAPE)
+    return _k.roi_align_grad(dY.contiguous(), R, tuple(X.shape), spatial_scale, sampling_ratio,
+                             layout='NCHW')
 
 
 def RoIContext(R, X, context_ratio=1.8):

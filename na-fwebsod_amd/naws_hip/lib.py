@@ -46,6 +46,8 @@ PROTOTYPES = {
     'naws_nchw_to_nhwc': [p, i32, i32, i32, i32, p, p],
     'naws_nhwc_to_nchw': [p, i32, i32, i32, i32, p, p],
     'naws_roi_pool_f_fwd': [p, i32, i32, i32, i32, i32, p, i32, p, i32, i32, f32, p, p, p],
+    'naws_roi_align_fwd': [p, i32, i32, i32, i32, p, i32, i32, i32, f32, i32, p, p],
+    'naws_roi_align_bwd': [p, p, i32, i32, i32, i32, i32, i32, i32, f32, i32, p, p],
     'naws_roi_context_fwd': [p, i32, f32, i32, i32, p, p, p],
     'naws_roi_loop_pool_fwd': [p, i32, i32, i32, i32, i32, p, i32, p, i32, i32, f32, p, p, p],
     'naws_roi_feature_boost_fwd': [p, p, i32, i32, p, p],

@@ -237,6 +237,57 @@ def roi_pool_f_grad(dy, argmax, rois, x_shape, layout='NCHW'):
     return dx
 
 
+def _roi_align_dims(fn, shape, layout):
+    if len(shape) != 4:
+        raise L.NawsError(fn, L.ERR_SHAPE)
+    if layout == 'NCHW':
+        n, c, h, w = shape
+    elif layout == 'NHWC':
+        n, h, w, c = shape
+    else:
+        raise L.NawsError(fn, L.ERR_ARG)
+    return int(n), int(c), int(h), int(w)
+
+
+def roi_align(x, rois, pooled_h=7, pooled_w=7, spatial_scale=0.125, sampling_ratio=0,
+              layout='NCHW', out=None):
+    """RoIAlign (include/naws.h a-2b): x [N,C,H,W] ('NCHW') or [N,H,W,C] ('NHWC'), rois [R,5] ->
+    y [R,C,ph,pw].  The kernel has one form, NHWC: an NCHW caller's x is transposed first."""
+    _chk(x, 'x'); _chk(rois, 'rois')
+    if rois.dim() != 2 or rois.shape[1] != 5:
+        raise L.NawsError('naws_roi_align_fwd', L.ERR_SHAPE)
+    n, c, h, w = _roi_align_dims('naws_roi_align_fwd', tuple(x.shape), layout)
+    r = rois.shape[0]
+    shape = (r, c, int(pooled_h), int(pooled_w))
+    if out is not None and (_chk(out, 'out').shape != shape):
+        raise L.NawsError('naws_roi_align_fwd', L.ERR_SHAPE)
+    xh = nchw_to_nhwc(x) if layout == 'NCHW' else x
+    y = out if out is not None else torch.empty(shape, device=x.device, dtype=_f32)
+    L.call('naws_roi_align_fwd', xh.data_ptr(), n, c, h, w, rois.data_ptr(), r, int(pooled_h),
+           int(pooled_w), float(spatial_scale), int(sampling_ratio), y.data_ptr(), _stream())
+    return y
+
+
+def roi_align_grad(dy, rois, x_shape, spatial_scale=0.125, sampling_ratio=0, layout='NCHW',
+                   out=None):
+    """RoIAlignGradient: dy [R,C,ph,pw] -> dx of shape x_shape in `layout` (zero-filled by the
+    entry; float atomic adds: reproducible to rounding, see include/naws.h).  `out`: the NHWC
+    gradient's buffer (layout 'NHWC' only)."""
+    _chk(dy, 'dy'); _chk(rois, 'rois')
+    if rois.dim() != 2 or rois.shape[1] != 5 or dy.dim() != 4 or dy.shape[0] != rois.shape[0]:
+        raise L.NawsError('naws_roi_align_bwd', L.ERR_SHAPE)
+    n, c, h, w = _roi_align_dims('naws_roi_align_bwd', tuple(x_shape), layout)
+    if dy.shape[1] != c:
+        raise L.NawsError('naws_roi_align_bwd', L.ERR_SHAPE)
+    if out is not None and (layout != 'NHWC' or _chk(out, 'out').shape != (n, h, w, c)):
+        raise L.NawsError('naws_roi_align_bwd', L.ERR_SHAPE)
+    dx = out if out is not None else torch.empty((n, h, w, c), device=dy.device, dtype=_f32)
+    L.call('naws_roi_align_bwd', dy.data_ptr(), rois.data_ptr(), rois.shape[0], n, c, h, w,
+           dy.shape[2], dy.shape[3], float(spatial_scale), int(sampling_ratio), dx.data_ptr(),
+           _stream())
+    return nhwc_to_nchw(dx) if layout == 'NCHW' else dx
+
+
 def roi_context(rois, max_h, max_w, ratio=1.8):
     """RoIContext: rois [R,5] -> (frame [R,9], context [R,9]); max_h / max_w are dims 2 / 3 of the
     padded image blob (include/naws.h: naws_roi_context_fwd)."""

@@ -1078,6 +1078,53 @@ int naws_voc_ap_fwd(const double* tp, const double* fp, const int64_t* cls_off, 
                     int64_t D, int K, double* rec, double* prec, double* ap07, double* ap_area,
                     void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * f-6  Test-time grid search over TEST.NMS x TEST.SCORE_THRESH x TEST.DETECTIONS_PER_IM (the
+ *      reference's tools/test_net_wsl_grid_search.py :157-187 runs box_results_with_nms_and_limit,
+ *      core/test_wsl.py:803-863, and the evaluation once per setting).  Here the per-setting work
+ *      is a selection: one NMS pass yields every threshold's survivors, a score threshold only
+ *      cuts a prefix of a list, and the image-wide cut needs one count and one score per
+ *      (image, NMS threshold).  Neither entry synchronises, allocates or uses atomics.
+ *      Errors (both), in this order: a negative count -> SHAPE; T < 1 (boxes not on 16 bytes) ->
+ *      ARG; a null pointer that the counts make required -> NULL; T > 32 (S or Lc > 64, a count
+ *      above 2^31 - 1) -> UNSUPPORTED; then, because they are read through a host pointer, a NaN
+ *      among the thresholds -> ARG.  The threshold and limit vectors are HOST arrays, copied into
+ *      the launch.  The offset vectors live on the device: the kernels check them (0 <= off[i] <=
+ *      off[i + 1] <= count) and a list / image that fails is reported in its status word (-2; a
+ *      list longer than 16384: -3) and touches nothing else; 0 = done.
+ *
+ * naws_nms_multi_fwd — greedy NMS (utils/cython_nms.pyx:36-87) of nlists lists at T thresholds in
+ *   one pass; one workgroup per list (the grid is capped and strides).  boxes fp32 [total][4]
+ *   (x1, y1, x2, y2), inside a list ALREADY in visiting order (descending score, equal scores by
+ *   ascending row); list_off int64 [nlists + 1].  Lists of 0 and 1 boxes are valid; up to 16384
+ *   boxes per list, the limit of naws_nms_sorted_fwd.  Per list a T-bit word supp[] starts at 0;
+ *   for i ascending: alive = ~supp[i]; a box with alive == 0 is skipped; for every j > i,
+ *   ovr = inter / (a_i + a_j - inter) in the arithmetic of naws_nms_sorted_fwd - fp32, +1 pixel
+ *   areas, inter = max(0, min(x2) - max(x1) + 1) * max(0, min(y2) - max(y1) + 1), every operation
+ *   rounded on its own - and supp[j] |= {t : ovr >= thresholds[t]} & alive (a NaN overlap
+ *   suppresses nothing).  -> survive uint32 [total]: bit t = 1 when the box is kept at
+ *   thresholds[t], which is the kept set of naws_nms_sorted_fwd at that threshold; bits T.. are 0.
+ *   A list of at most 2048 boxes is walked in LDS, a longer one in memory (survive is then the
+ *   working state).  status int32 [nlists].
+ * naws_grid_cut_fwd — what the image-wide cut (core/test_wsl.py:849-863) needs.  survive uint32
+ *   [N] and score fp32 [N]: an image's candidates of ALL classes in descending score, the images
+ *   segmented by img_off int64 [I + 1]; any segment length.  One wave per (image, t).  ->
+ *   count int32 [I][T][S]: the candidates with bit t set and score > score_thresholds[s];
+ *   kth fp32 [I][T][Lc]: the score of the limits[l]-th candidate (1-based) with bit t set, and
+ *   -inf when fewer have it or limits[l] <= 0.  A candidate is then kept at (t, s, l) when
+ *     bit t and score > score_thresholds[s] and
+ *     (limits[l] <= 0 or count[img][t][s] <= limits[l] or score >= kth[img][t][l])
+ *   - the L-th best survivor above a score threshold is the L-th best survivor whenever more than
+ *   L lie above it; ties at the cut keep more than L, as np.sort(...)[-L] and `>=` do.
+ *   status int32 [I].
+ * ------------------------------------------------------------------------ */
+int naws_nms_multi_fwd(const float* boxes, const int64_t* list_off, int64_t total, int64_t nlists,
+                       const float* thresholds, int T, uint32_t* survive, int32_t* status,
+                       void* stream);
+int naws_grid_cut_fwd(const uint32_t* survive, const float* score, const int64_t* img_off, int64_t N,
+                      int64_t I, int T, const float* score_thresholds, int S, const int32_t* limits,
+                      int Lc, int32_t* count, float* kth, int32_t* status, void* stream);
+
 /* ---- process-wide state and tuning (no reference counterpart) ------------------------------ */
 /* Kernels that need more than 64 KB of dynamic LDS have that limit raised once per (kernel,
  * device) pair; the library remembers which pairs are done.  After hipDeviceReset() - which

@@ -85,6 +85,8 @@ PROTOTYPES = {
     'naws_stat_accumulate': [p, p, i32, i32, p, p, p],
     'naws_voc_match_fwd': [p, p, p, p, p, i64, i64, i64, C.c_double, p, p, p, p, p],
     'naws_voc_ap_fwd': [p, p, p, p, i64, i32, p, p, p, p, p],
+    'naws_nms_multi_fwd': [p, p, i64, i64, p, i32, p, p, p],
+    'naws_grid_cut_fwd': [p, p, p, i64, i64, i32, p, i32, p, i32, p, p, p, p],
     'naws_unary_f32': [i32, p, i64, f32, f32, p, p],
     'naws_binary_f32': [i32, p, i32, i32, p, i32, i32, p, i32, i32, p],
     'naws_softmax_rows_fwd': [p, i32, i32, p, p],

@@ -1760,6 +1760,44 @@ def voc_ap(tp, fp, cls_off, npos):
     return rec, prec, ap07, ap_area
 
 
+def nms_multi(boxes, list_off, thresholds):
+    """boxes fp32 [N,4] (every list already in visiting order), list_off int64 [lists+1],
+    thresholds: 1..32 host floats -> (survive int32 [N]: bit t = kept at thresholds[t], status
+    int32 [lists]); see naws_nms_multi_fwd."""
+    _chk(boxes, 'boxes'); _chk(list_off, 'list_off', torch.int64)
+    n, lists = boxes.shape[0], list_off.numel() - 1
+    if tuple(boxes.shape) != (n, 4) or lists < 0:
+        raise L.NawsError('naws_nms_multi_fwd', L.ERR_SHAPE)
+    thr = np.ascontiguousarray(thresholds, np.float32).reshape(-1)
+    dev = boxes.device
+    survive = torch.zeros((n,), device=dev, dtype=torch.int32)
+    status = torch.zeros((lists,), device=dev, dtype=torch.int32)
+    L.call('naws_nms_multi_fwd', boxes.data_ptr(), list_off.data_ptr(), n, lists, thr.ctypes.data,
+           int(thr.size), survive.data_ptr(), status.data_ptr(), _stream())
+    return survive, status
+
+
+def grid_cut(survive, score, img_off, num_nms, score_thresholds, limits):
+    """survive int32 [N] (nms_multi's words) and score fp32 [N], every image's candidates in
+    descending score, img_off int64 [I+1]; num_nms = T; score_thresholds / limits host values ->
+    (count int32 [I,T,S], kth fp32 [I,T,Lc], status int32 [I]); see naws_grid_cut_fwd."""
+    _chk(survive, 'survive', torch.int32); _chk(score, 'score'); _chk(img_off, 'img_off', torch.int64)
+    n, imgs = survive.numel(), img_off.numel() - 1
+    if score.numel() != n or imgs < 0:
+        raise L.NawsError('naws_grid_cut_fwd', L.ERR_SHAPE)
+    sth = np.ascontiguousarray(score_thresholds, np.float32).reshape(-1)
+    lim = np.ascontiguousarray(limits, np.int32).reshape(-1)
+    t = int(num_nms)
+    dev = survive.device
+    count = torch.zeros((imgs, max(t, 0), sth.size), device=dev, dtype=torch.int32)
+    kth = torch.zeros((imgs, max(t, 0), lim.size), device=dev, dtype=_f32)
+    status = torch.zeros((imgs,), device=dev, dtype=torch.int32)
+    L.call('naws_grid_cut_fwd', survive.data_ptr(), score.data_ptr(), img_off.data_ptr(), n, imgs, t,
+           sth.ctypes.data if sth.size else 0, int(sth.size), lim.ctypes.data if lim.size else 0,
+           int(lim.size), count.data_ptr(), kth.data_ptr(), status.data_ptr(), _stream())
+    return count, kth, status
+
+
 class RowmaxTable(object):
     """[(first element, end element, row length, first rowmax index)] for acm_sgd_update."""
 

@@ -87,6 +87,27 @@ int naws_conv3x3_winograd_nhwc_fwd(const float* X, const float* U, const float* 
 int naws_maxpool2x2_nhwc_fwd(const float* X, int N, int H, int W, int C, int stride,
                              float* Y, void* stream);
 
+/* MaxPool kernel 3, pad 1, stride 1 or 2, NHWC in/out: the pools of the
+ * DeepLab body (ref: detectron/modeling/VGG16.py:94-140, pool1..pool3 at
+ * stride 2, pool4 at stride 1 under WSL.DILATION 2).  The operator is Caffe2's
+ * built-in MaxPool (pytorch v1.3.0 caffe2/operators/pool_op.cc); its source is
+ * vendored neither in the reference tree nor on the build machine: parity
+ * with a reference-executed number is UNPINNED, the arithmetic below is the
+ * contract.
+ *   Ho = (H + 2 - 3) / stride + 1 (floor, the legacy rule of the 2x2 entry),
+ *   Wo likewise.  Y[n,yo,xo,c] = the maximum of X[n,y,x,c] over the rows
+ *   max(yo*stride-1, 0) .. min(yo*stride+1, H-1) and the same clipped range of
+ *   columns.  Padding is never a candidate: the maximum does not start from 0
+ *   (an all-negative window returns its largest element), and every window
+ *   holds at least one real pixel.  fmaxf semantics (a NaN is skipped); a
+ *   float max does not round, so the result is exact.
+ * Errors, all before any launch: a non-positive dim -> SHAPE; a stride other
+ * than 1 or 2 -> ARG; C % 4 != 0 or a pointer not 16-byte aligned -> ARG; a
+ * missing pointer -> NULL.  There is no gradient entry: nothing builds one
+ * (the DeepLab body runs frozen only). */
+int naws_maxpool3x3_nhwc_fwd(const float* X, int N, int H, int W, int C, int stride,
+                             float* Y, void* stream);
+
 int naws_nchw_to_nhwc(const float* X, int N, int C, int H, int W, float* Y, void* stream);
 int naws_nhwc_to_nchw(const float* X, int N, int H, int W, int C, float* Y, void* stream);
 

@@ -6,7 +6,9 @@ Replaces `workspace.RunNet(model.net)` + the Caffe2 dag executor of the referenc
   * FUSED — chosen when the recorded op list is exactly the na_wsddn graph (the one
     `VGG16.add_VGG16_conv5_body_origin` + `webly_heads.add_VGG16_roi_2fc_noise_head` +
     `add_webly_outputs` + `add_webly_losses` emit): the blobs run through
-    naws_hip.engine.WsddnEngine (fused kernels, any number of images per process).
+    naws_hip.engine.WsddnEngine (fused kernels, any number of images per process).  The same
+    graph over `VGG16.add_VGG16_conv5_body_deeplab` (MODEL.CONV_BODY) is fused too: its chain
+    pools with kernel 3 / pad 1.  Any other body (`add_VGG16_conv4_body_origin`) runs op by op.
   * INTERPRETED — any other graph made of the supported operators runs op by op through
     detectron.ops (same HIP kernels, one launch group per op, reference semantics of one
     image per process).  It is also the cross-check of the fused plan in the tests.
@@ -26,18 +28,47 @@ def _signature(ops_list):
     return [(o.type, tuple(o.inputs), o.outputs[0]) for o in ops_list]
 
 
-def canonical_na_wsddn_signature(train, num_classes):
-    """The op list the reference builders emit for the hot-path config under the current cfg."""
+def _pool_args(ops_list):
+    """(kernel, pad, stride) of every MaxPool: what tells the conv bodies apart (the signature
+    carries names only, and the DeepLab body's are the origin body's)."""
+    return [(o.args.get('kernel'), o.args.get('pad'), o.args.get('stride'))
+            for o in ops_list if o.type == 'MaxPool']
+
+
+def _canonical_na_wsddn_ops(train, num_classes):
+    """The canonical model's ops with the conv body MODEL.CONV_BODY names (the origin body when the
+    key is empty, as before there was a second one); None for a body the fused engine does not run."""
     from detectron.modeling.detector import DetectionModelHelper
     from detectron.modeling import VGG16, webly_heads
+    from naws_hip.engine import body_of
+    body = body_of(cfg.MODEL.CONV_BODY or 'VGG16.add_VGG16_conv5_body_origin')
+    if body is None:
+        return None
     m = DetectionModelHelper(name='canon', train=train, num_classes=num_classes, init_params=train)
-    blob, dim, scale = VGG16.add_VGG16_conv5_body_origin(m)
+    blob, dim, scale = getattr(VGG16, 'add_VGG16_conv5_body_' + body)(m)
     m.StopGradient(blob, blob)
     ls, dims = webly_heads.add_VGG16_roi_2fc_noise_head(m, blob, dim, scale)
     webly_heads.add_webly_outputs(m, ls, dims)
     if train:
         webly_heads.add_webly_losses(m)
-    return _signature(m.net.ops)
+    return m.net.ops
+
+
+def canonical_na_wsddn_signature(train, num_classes):
+    """The op list the reference builders emit for the hot-path config under the current cfg, over
+    the configured conv body; None when that body has no fused plan (the caller then runs op by
+    op)."""
+    ops_list = _canonical_na_wsddn_ops(train, num_classes)
+    return None if ops_list is None else _signature(ops_list)
+
+
+def _is_canonical_na_wsddn(model, sig):
+    """The model's op list is the canonical one: the same names AND the same pools (the DeepLab
+    body differs from the origin body by its MaxPool arguments and, under FREEZE_AT: 2, the
+    StopGradient at pool2 alone)."""
+    canon = _canonical_na_wsddn_ops(model.train, model.num_classes)
+    return (canon is not None and sig == _signature(canon) and
+            _pool_args(model.net.ops) == _pool_args(canon))
 
 
 def _fill(init, shape, gen, device):
@@ -76,13 +107,16 @@ class NetExecutor(object):
                     not cfg.WSL.CENTER_LOSS and
                     # likewise RoIAlign: the engine pools with RoIPoolF whatever the op list says
                     cfg.FAST_RCNN.ROI_XFORM_METHOD == 'RoIPoolF' and
-                    sig == canonical_na_wsddn_signature(model.train, model.num_classes))
+                    # the canonical list is built over the conv body MODEL.CONV_BODY names; a body
+                    # without a fused chain (the conv4 body, a user's own) has none and runs op by op
+                    _is_canonical_na_wsddn(model, sig))
         self.plan = 'fused' if fused_ok else 'interpreted'
         self.engine = None
         if fused_ok:
-            from naws_hip.engine import WsddnEngine
+            from naws_hip.engine import WsddnEngine, body_of
             self.engine = WsddnEngine(
                 model.num_classes, device, dilation=cfg.WSL.DILATION,
+                body=body_of(cfg.MODEL.CONV_BODY or 'VGG16.add_VGG16_conv5_body_origin'),
                 roi_size=cfg.FAST_RCNN.ROI_XFORM_RESOLUTION,
                 dropout=0.0 if disable_dropout else 0.5,
                 is_mean=cfg.WSL.MEAN_LOSS, momentum=cfg.SOLVER.MOMENTUM,

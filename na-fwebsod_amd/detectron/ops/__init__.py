@@ -19,6 +19,8 @@ Caffe2 built-ins used by the path (pytorch v1.3.0 caffe2/operators, restated): R
 (+Gradient), RoIAlign(+Gradient), Conv(+Gradient), Relu, MaxPool(+Gradient), FC, Dropout, Softmax, Transpose,
 Add/Sub/Mul/Div (numpy-style broadcast), ReduceSum, Log, Scale, ReplaceNaN, MatMul, LeakyRelu, Clip, ConstantFill,
 Shape/Cast (host), AveragedLoss, Accuracy, StopGradient, Concat/Split (views).
+MaxPool takes (kernel 2, pad 0, stride 1 | 2) - the origin body, with a gradient - and (kernel 3,
+pad 1, stride 1 | 2) - the DeepLab body (VGG16.py:94-140), forward only: that body runs frozen.
 
 Tensors are NCHW / row-major like the reference blobs.  There is no CPU fallback: CPU
 tensors raise TypeError, shape violations raise naws_hip.lib.NawsError where the reference
@@ -427,6 +429,11 @@ def ReluGradient(Y, dY):
 
 
 def MaxPool(X, kernel=2, pad=0, stride=2):
+    """(kernel 2, pad 0) of the origin body or (kernel 3, pad 1, stride 1 | 2) of the DeepLab body
+    (VGG16.py:94-140; padding never a candidate, floor output size).  The 3x3 arithmetic is stated
+    in include/naws.h; Caffe2's own operator was never executed against it."""
+    if (kernel, pad) == (3, 1) and stride in (1, 2):
+        return _k.nhwc_to_nchw(_k.maxpool3x3_nhwc(_k.nchw_to_nhwc(X), stride))
     if kernel != 2 or pad != 0:
         raise NawsError('MaxPool', _L.ERR_UNSUPPORTED)
     return _k.nhwc_to_nchw(_k.maxpool2x2_nhwc(_k.nchw_to_nhwc(X), stride))

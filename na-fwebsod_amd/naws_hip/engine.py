@@ -54,19 +54,39 @@ VGG16_CONVS = [
 # of max|y| from its weights.
 ConvStep = collections.namedtuple('ConvStep',
                                   'name form cin cout dilation direct_alt pool2 weight_bound')
-PoolStep = collections.namedtuple('PoolStep', 'form stride')          # form 'pool'
+# form 'pool': kernel 2 / pad 0 (the origin body); 'pool3': kernel 3 / pad 1 (the DeepLab body)
+PoolStep = collections.namedtuple('PoolStep', 'form stride')
+_POOL_FORMS = ('pool', 'pool3')
 _H2_FORMS = ('h2_direct', 'h2_wino2', 'h2_wino4')
+BODIES = ('origin', 'deeplab')
 
 
-def conv_plan(mfma_dtype, dilation, wino_f4_min_cin):
+def pooled_size(step, h, w):
+    """The output size of PoolStep `step` on an h x w map (floor, the legacy pooling rule)."""
+    pad2, k = (2, 3) if step.form == 'pool3' else (0, 2)
+    return (h + pad2 - k) // step.stride + 1, (w + pad2 - k) // step.stride + 1
+
+
+def body_of(conv_body):
+    """MODEL.CONV_BODY -> the conv_plan() body it names, or None (no fused chain for it)."""
+    return {'VGG16.add_VGG16_conv5_body_origin': 'origin',
+            'VGG16.add_VGG16_conv5_body_deeplab': 'deeplab'}.get(conv_body)
+
+
+def conv_plan(mfma_dtype, dilation, wino_f4_min_cin, body='origin'):
     """The form of every VGG16_CONVS entry (a ConvStep or PoolStep each) under the arithmetic plan
-    `mfma_dtype`; dilation: the engine's (2: conv5_x dilated behind a stride-1 pool4)."""
+    `mfma_dtype`; dilation: the engine's (2: conv5_x dilated behind a stride-1 pool4).  body
+    'deeplab' (VGG16.py:94-140): the four pools are kernel 3 / pad 1 ('pool3') at the same strides
+    and none is taken in a conv epilogue (that pool is the 2x2 one); every conv form stays."""
     if mfma_dtype not in ('fp32', 'fp32x3', 'fp16x2', 'bf16'):
         raise ValueError('unknown mfma_dtype %r' % (mfma_dtype,))
+    if body not in BODIES:
+        raise ValueError('unknown conv body %r' % (body,))
     plan = []
     for i, item in enumerate(VGG16_CONVS):
         if item[0].startswith('pool'):
-            plan.append(PoolStep('pool', item[1] if len(item) > 1 else 1 if dilation == 2 else 2))
+            plan.append(PoolStep('pool3' if body == 'deeplab' else 'pool',
+                                 item[1] if len(item) > 1 else 1 if dilation == 2 else 2))
             continue
         name, cin, cout, dil = item
         wino = cin >= 128 and cout >= 256          # conv3_1 .. conv5_3
@@ -91,7 +111,7 @@ def conv_plan(mfma_dtype, dilation, wino_f4_min_cin):
         # (F(4x4) layers never switch to the direct form: 42.4 vs 43.5 ms per TTA image with it
         # taking over at the large scales, 44.5 for F(2x2) with it)
         direct_alt = form == 'h2_wino2'
-        pool2 = (i + 1 < len(VGG16_CONVS) and VGG16_CONVS[i + 1][0] == 'pool'
+        pool2 = (body == 'origin' and i + 1 < len(VGG16_CONVS) and VGG16_CONVS[i + 1][0] == 'pool'
                  and (direct_alt or form in ('h2_direct', 'x3_direct', 'bf16_wp')))
         plan.append(ConvStep(name, form, cin, cout, dil or (2 if dilation == 2 else 1), direct_alt,
                              pool2, form == 'c3' and mfma_dtype == 'fp16x2'))
@@ -193,7 +213,9 @@ class WsddnEngine(object):
                  momentum=0.9, weight_decay=5e-4, iter_size=1, gpu_num=1, seed=11,
                  process_group=None, world_size=1, allreduce_chunks=0, freeze_conv_body=True,
                  mfma_dtype='fp16x2', scale_momentum=True, scale_momentum_threshold=1.1,
-                 sharded_update=False, rank=None, pipeline_update=None):
+                 sharded_update=False, rank=None, pipeline_update=None, body='origin'):
+        if body not in BODIES:
+            raise ValueError('unknown conv body %r' % (body,))
         if not freeze_conv_body:
             raise NotImplementedError('only TRAIN.FREEZE_CONV_BODY: True is on the hot path '
                                       '(SURVEY.md fact 2): the conv body has no backward')
@@ -203,6 +225,7 @@ class WsddnEngine(object):
         self.C = num_classes - 1
         self.device = device
         self.dilation = dilation
+        self.body = body             # 'origin' | 'deeplab' (3x3 / pad-1 pools): conv_plan()
         self.roi_size = roi_size
         self.spatial_scale = 1.0 / 8.0 if dilation == 2 else 1.0 / 16.0
         self.dropout = float(dropout)
@@ -405,8 +428,8 @@ class WsddnEngine(object):
         """blobs: name_w [O,I,3,3], name_b [O] (reference layout).  Packs each layer once, for the
         form conv_plan() gives it."""
         layers = []
-        for s in conv_plan(self.mfma_dtype, self.dilation, self.WINO_F4_MIN_CIN):
-            if s.form == 'pool':
+        for s in conv_plan(self.mfma_dtype, self.dilation, self.WINO_F4_MIN_CIN, body=self.body):
+            if s.form in _POOL_FORMS:
                 layers.append(ConvLayer(s, None, None, None, None, None))
                 continue
             for key, shape in ((s.name + '_w', (s.cout, s.cin, 3, 3)), (s.name + '_b', (s.cout,))):
@@ -510,6 +533,10 @@ class WsddnEngine(object):
                  if any(lay.step.form in _H2_FORMS for lay in layers) else None)
         for k, lay in enumerate(layers):
             s = lay.step
+            if s.form == 'pool3':
+                # (a max over real pixels only lowers max|x|: the bound handed on stays valid)
+                x = ops.maxpool3x3_nhwc(x, s.stride)
+                continue
             if s.form == 'pool':
                 if not pooled:
                     x = ops.maxpool2x2_nhwc(x, s.stride)
@@ -585,8 +612,8 @@ class WsddnEngine(object):
             self._roi_maps_of = (res.data_ptr(), res._version)
             return res
         h, w = data.shape[2], data.shape[3]
-        for s in (lay.step for lay in self.conv_layers if lay.step.form == 'pool'):
-            h, w = (h - 2) // s.stride + 1, (w - 2) // s.stride + 1
+        for s in (lay.step for lay in self.conv_layers if lay.step.form in _POOL_FORMS):
+            h, w = pooled_size(s, h, w)
         out = torch.empty((n, h, w, 512), device=self.device, dtype=torch.float32)
         # (bf16 plan: RoIPoolF writes fc6's one-plane operand over the same maps)
         self._roi_maps = ((torch.empty_like(out), torch.empty_like(out))

@@ -38,6 +38,7 @@ PROTOTYPES = {
     'naws_conv3x3_nhwc_fwd': [p, p, p, i32, i32, i32, i32, i32, i32, i32, p, p],
     'naws_maxpool2x2_nhwc_fwd': [p, i32, i32, i32, i32, i32, p, p],
     'naws_maxpool2x2_nhwc_bwd': [p, p, p, i32, i32, i32, i32, i32, p, p],
+    'naws_maxpool3x3_nhwc_fwd': [p, i32, i32, i32, i32, i32, p, p],
     'naws_conv3x3_dgrad_pack_weight': [p, i32, i32, p, p],
     'naws_conv3x3_nhwc_wgrad': [p, p, i32, i32, i32, i32, i32, i32, p, p, p, p],
     'naws_roi_pool_f_bwd': [p, p, p, i32, i32, i32, i32, i32, i32, i32, i32, p, p],

@@ -115,6 +115,23 @@ def maxpool2x2_nhwc(x, stride, out=None):
     return y
 
 
+def maxpool3x3_nhwc(x, stride, out=None):
+    """MaxPool kernel 3 / pad 1 / stride 1 or 2 (the DeepLab body's pools): [n, h, w, c] ->
+    [n, (h - 1) // stride + 1, (w - 1) // stride + 1, c], padding never a candidate."""
+    _chk(x, 'x')
+    n, h, w, c = x.shape
+    if stride not in (1, 2):
+        raise L.NawsError('naws_maxpool3x3_nhwc_fwd', L.ERR_ARG)
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    if out is not None:
+        _chk(out, 'out')
+        if tuple(out.shape) != (n, ho, wo, c):
+            raise L.NawsError('naws_maxpool3x3_nhwc_fwd', L.ERR_SHAPE)
+    y = out if out is not None else torch.empty((n, ho, wo, c), device=x.device, dtype=_f32)
+    L.call('naws_maxpool3x3_nhwc_fwd', x.data_ptr(), n, h, w, c, stride, y.data_ptr(), _stream())
+    return y
+
+
 def nchw_to_nhwc(x):
     _chk(x, 'x')
     n, c, h, w = x.shape

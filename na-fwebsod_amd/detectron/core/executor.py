@@ -11,7 +11,8 @@ Replaces `workspace.RunNet(model.net)` + the Caffe2 dag executor of the referenc
     pools with kernel 3 / pad 1.  Any other body (`add_VGG16_conv4_body_origin`) runs op by op.
   * INTERPRETED — any other graph made of the supported operators runs op by op through
     detectron.ops (same HIP kernels, one launch group per op, reference semantics of one
-    image per process).  It is also the cross-check of the fused plan in the tests.
+    image per process); detectron/core/op_table.py declares each operator once.  It is also
+    the cross-check of the fused plan in the tests.
 
 Blob names are the reference's unscoped names (one process per GPU).
 """
@@ -19,6 +20,7 @@ import numpy as np
 import torch
 
 from detectron.core.config import cfg
+from detectron.core.op_table import TABLE
 import detectron.ops as O
 from naws_hip import lib as L
 from naws_hip import ops as K
@@ -131,7 +133,7 @@ class NetExecutor(object):
             if self.ims != 1:
                 raise NotImplementedError('the op-by-op plan follows the reference: one image '
                                           'per process (wsl_heads.py:214)')
-            self._stats, self._sgd = {}, {}
+            self._state, self._sgd = {}, {}     # per-op objects by forward op index; SGD by param
 
     # -------------------------------------------------------------- parameters
     def init_params(self, seed=None):
@@ -234,8 +236,8 @@ class NetExecutor(object):
             self._forward(idx, op, ws)
         if not self.model.train:
             return
-        for op in self.model.grad_ops:
-            self._backward(op, ws)
+        for op, fwd_idx in zip(self.model.grad_ops, self.model.grad_fwd_idx):
+            self._backward(op, ws, fwd_idx)
         params = self.model.TrainableParams()
         if self.pg is not None and self.world > 1:
             import torch.distributed as dist
@@ -247,7 +249,7 @@ class NetExecutor(object):
             # iteration would multiply them by `world` until they overflow (the reference's appended
             # all-reduce does; harmless there too, as nothing reads them), so the sum stops with it.
             for idx, op in enumerate(self.model.net.ops):
-                if op.type == 'CenterLoss' and self._stats[idx].contributed:
+                if op.type == 'CenterLoss' and self._state[idx].contributed:
                     dist.all_reduce(ws[op.inputs[4]], group=self.pg)
                     dist.all_reduce(ws[op.inputs[5]], group=self.pg)
         for p in params:
@@ -261,196 +263,45 @@ class NetExecutor(object):
             self._sgd[p](ws[self.model.param_to_grad[p]].contiguous(), ws[p + '_momentum'],
                          self.lr, ws[p], ws[p + '_acmgrad'])
 
-    def _forward(self, idx, op, ws):
-        t, a = op.type, op.args
-        x = [ws[n] for n in op.inputs if n in ws]
-        out = op.outputs
-        if t == 'Conv':
-            ws[out[0]] = O.Conv(x[0], x[1], x[2], kernel=a.get('kernel', 3), pad=a.get('pad', 1),
-                                stride=a.get('stride', 1), dilation=a.get('dilation', 1))
-        elif t == 'Relu':
-            ws[out[0]] = O.Relu(x[0])
-        elif t == 'MaxPool':
-            ws[out[0]] = O.MaxPool(x[0], kernel=a['kernel'], pad=a['pad'], stride=a['stride'])
-        elif t == 'StopGradient':
-            ws[out[0]] = x[0]
-        elif t == 'RoIPoolF':
-            ws[out[0]], ws[out[1]] = O.RoIPoolF(x[0], x[1], a['pooled_h'], a['pooled_w'],
-                                                a['spatial_scale'])
-        elif t == 'RoIAlign':
-            ws[out[0]] = O.RoIAlign(x[0], x[1], a['pooled_h'], a['pooled_w'], a['spatial_scale'],
-                                    a.get('sampling_ratio', 0))
-        elif t == 'RoIContext':      # inputs (rois, data): the clamp bounds are the image blob's dims
-            ws[out[0]], ws[out[1]] = O.RoIContext(x[0], ws['data'],
-                                                  context_ratio=a.get('context_ratio', 1.8))
-        elif t == 'RoILoopPool':
-            ws[out[0]], ws[out[1]] = O.RoILoopPool(x[0], x[1], a['pooled_h'], a['pooled_w'],
-                                                   a['spatial_scale'])
-        elif t == 'RoIFeatureBoost':
-            ws[out[0]] = O.RoIFeatureBoost(x[0], x[1])
-        elif t == 'FC':
-            ws[out[0]] = O.FC(x[0], x[1], x[2])
-        elif t == 'Dropout':
-            y, mask = O.Dropout(x[0], ratio=a.get('ratio', 0.5),
-                                is_test=a.get('is_test', False) or self.disable_dropout,
-                                seed=(cfg.RNG_SEED * 1000003 + self.step * 131 + idx))
-            ws[out[0]] = y
-            ws[out[1]] = mask
-        elif t == 'Softmax':
-            ws[out[0]] = O.Softmax(x[0], axis=a.get('axis', 1))
-        elif t == 'Transpose':
-            ws[out[0]] = O.Transpose(x[0], axes=a.get('axes', (1, 0)))
-        elif t in ('Add', 'Sub', 'Mul', 'Div'):
-            ws[out[0]] = getattr(O, t)(x[0], x[1])
-        elif t == 'ReduceSum':
-            ws[out[0]] = O.ReduceSum(x[0], axes=a.get('axes', [0]), keepdims=a.get('keepdims', True))
-        elif t == 'RoIIoU':
-            ws[out[0]] = O.RoIIoU(x[0])
-        elif t == 'Log':
-            ws[out[0]] = O.Log(x[0])
-        elif t == 'Scale':
-            ws[out[0]] = O.Scale(x[0], scale=a.get('scale', 1.0))
-        elif t == 'ReplaceNaN':
-            ws[out[0]] = O.ReplaceNaN(x[0], value=a.get('value', 0.0))
-        elif t == 'MatMul':
-            ws[out[0]] = O.MatMul(x[0], x[1])
-        elif t == 'LeakyRelu':
-            ws[out[0]] = O.LeakyRelu(x[0], alpha=a.get('alpha', 0.01))
-        elif t == 'Shape':
-            ws[out[0]] = [x[0].shape[i] for i in a.get('axes', range(x[0].dim()))]
-        elif t == 'Cast':
-            ws[out[0]] = torch.tensor([float(v) for v in x[0]], device=self.device)
-        elif t == 'Clip':
-            ws[out[0]] = O.Clip(x[0], min=a.get('min', -3.4e38), max=a.get('max', 3.4e38))
-        elif t == 'ConstantFill':
-            ws[out[0]] = O.ConstantFill(like=x[0] if x else None, shape=a.get('shape'),
-                                        value=a.get('value', 0.0), device=self.device)
-        elif t == 'Stat':
-            if idx not in self._stats:
-                self._stats[idx] = O.Stat(display=a.get('display', 1280), prefix=a.get('prefix', ''))
-            ws[out[0]], ws[out[1]] = self._stats[idx](x[0].reshape(-1), x[1].reshape(-1),
-                                                      gpu_id=self.rank)
-        elif t == 'WeightedCrossEntropyWithLogits':
-            ws[out[0]] = O.WeightedCrossEntropyWithLogits(x[0], x[1], x[2],
-                                                          is_mean=a.get('is_mean', False))
-        elif t == 'CrossEntropyWithLogits':
-            ws[out[0]] = O.CrossEntropyWithLogits(x[0], x[1], is_mean=a.get('is_mean', False))
-        elif t == 'AveragedLoss':
-            ws[out[0]] = O.AveragedLoss(x[0])
-        elif t == 'MinEntropyLoss':
-            ws[out[0]] = O.MinEntropyLoss(x[0], x[1])
-        elif t == 'Accuracy':
-            ws[out[0]] = O.Accuracy(x[0], x[1])
-        elif t == 'RoILabel':
-            if idx not in self._stats:
-                keys = ('display', 'uuid', 'fg_thresh', 'bg_thresh_hi', 'bg_thresh_lo', 'num_pos',
-                        'num_neg', 'top_k')
-                self._stats[idx] = O.RoILabel(**{k: a[k] for k in keys if k in a})
-            ws[out[0]], ws[out[1]] = self._stats[idx](*x)
-        elif t == 'SoftmaxWithLossN':
-            ws[out[0]], ws[out[1]] = O.SoftmaxWithLossN(x[0], x[1], x[2] if len(x) > 2 else None,
-                                                        scale=a.get('scale', 1.0))
-        elif t == 'RoIEntropy':
-            if idx not in self._stats:
-                self._stats[idx] = O.RoIEntropy(display=a.get('display', 1280),
-                                                num_classes=a.get('num_classes', 20),
-                                                rm_bg=a.get('rm_bg', True))
-            ws[out[0]] = self._stats[idx](x[0], x[1])
-        elif t == 'CenterLoss':       # one object per op index: the gradient half shares it
-            if idx not in self._stats:
-                keys = ('top_k', 'update', 'lr', 'display', 'max_iter', 'ignore_label')
-                self._stats[idx] = O.CenterLoss(**{k: a[k] for k in keys if k in a})
-                self._stats[('CenterLoss', out[0])] = self._stats[idx]
-            ws[out[0]], ws[out[1]], ws[out[2]], ws[out[3]] = self._stats[idx].forward(*x[:6])
-        elif t == 'BoxWithNMSLimit':
-            ws[out[0]], ws[out[1]], ws[out[2]] = O.BoxWithNMSLimit(
-                x[0], x[1], score_thresh=a.get('score_thresh', 0.05), nms=a.get('nms', 0.3),
-                detections_per_im=a.get('detections_per_im', 100))
-        elif t == 'Mean':
-            ws[out[0]] = O.Mean(*x)
-        elif t == 'Max':
-            ws[out[0]] = O.Max(x[0], x[1])
-        elif t == 'Tile':
-            ws[out[0]] = O.Tile(x[0], tiles=a.get('tiles', 1), axis=a.get('axis', 1))
-        elif t == 'Split':
-            parts = torch.split(x[0], a['split'], dim=a.get('axis', 1))
-            for n, p in zip(out, parts):
-                ws[n] = p
-        elif t == 'Concat':
-            ws[out[0]] = torch.cat(x, dim=a.get('axis', 1)).contiguous()
-        else:
-            raise NotImplementedError('operator {} is not on the MI355X hot path'.format(t))
+    def dropout_seed(self, idx):
+        """A Dropout op's seed: the run's, the iteration and the op's place in the net."""
+        return cfg.RNG_SEED * 1000003 + self.step * 131 + idx
 
-    def _backward(self, op, ws):
+    @staticmethod
+    def _gather(op, ws):
+        """The values of op.inputs; a name the workspace does not hold is an error before any
+        kernel runs, never a shift of the later inputs."""
+        for n in op.inputs:
+            if n not in ws:
+                raise KeyError('{} -> {}: input blob {} is not in the workspace'.format(
+                    op.type, op.outputs[0] if op.outputs else '', n))
+        return [ws[n] for n in op.inputs]
+
+    def _forward(self, idx, op, ws):
+        e = TABLE.get(op.type)
+        if e is None or e.forward is None:
+            raise NotImplementedError('operator {} is not on the MI355X hot path'.format(op.type))
+        x = self._gather(op, ws)
+        if e.state is not None and idx not in self._state:
+            self._state[idx] = e.state(op)      # one object per op: the gradient half shares it
+        for n, v in zip(op.outputs, e.forward(self, idx, op, x)):
+            ws[n] = v
+
+    def _backward(self, op, ws, fwd_idx=None):
+        """fwd_idx: the forward op's index (model.grad_fwd_idx), where its state is kept."""
         t, a = op.type[:-len('Gradient')], op.args
-        n_in = len(a['_gin'])
-        ins, outs = op.inputs[:n_in], op.inputs[n_in:]
-        gout = [ws[g] if g else None for g in a['_gout']]
-        res = [None] * n_in
-        if t == 'FC':
-            dW, db, dX = O.FCGradient(ws[ins[0]], ws[ins[1]], gout[0].contiguous(),
-                                      need_dx=a['_gin'][0] is not None)
-            res = [dX, dW, db]
-        elif t == 'Conv':
-            dW, db, dX = O.ConvGradient(ws[ins[0]], ws[ins[1]], gout[0], kernel=a.get('kernel', 3),
-                                        pad=a.get('pad', 1), stride=a.get('stride', 1),
-                                        dilation=a.get('dilation', 1),
-                                        need_dx=a['_gin'][0] is not None)
-            res = [dX, dW, db]
-        elif t == 'MaxPool':
-            res = [O.MaxPoolGradient(ws[ins[0]], ws[outs[0]], gout[0], kernel=a['kernel'],
-                                     pad=a['pad'], stride=a['stride'])]
-        elif t == 'RoIPoolF':      # outputs Y, argmax: the forward's own selection
-            res = [O.RoIPoolFGradient(ws[ins[0]], ws[ins[1]], ws[outs[1]], gout[0]), None]
-        elif t == 'RoIAlign':      # one output: the geometry is rebuilt from the rois
-            res = [O.RoIAlignGradient(ws[ins[0]], ws[ins[1]], gout[0], a['pooled_h'], a['pooled_w'],
-                                      a['spatial_scale'], a.get('sampling_ratio', 0)), None]
-        elif t == 'Relu':
-            res = [O.ReluGradient(ws[outs[0]], gout[0])]
-        elif t == 'Dropout':
-            res = [gout[0] if ws[outs[1]] is None else
-                   O.DropoutGradient(gout[0], ws[outs[1]], a.get('ratio', 0.5))]
-        elif t == 'Softmax':
-            res = [O.SoftmaxGradient(ws[outs[0]], gout[0])]
-        elif t == 'Transpose':
-            res = [O.Transpose(gout[0])]
-        elif t == 'Mul':
-            res = [O.Mul(gout[0], ws[ins[1]]), O.Mul(gout[0], ws[ins[0]])]
-        elif t == 'Add':
-            res = [gout[0], gout[0]]
-        elif t == 'Sub':
-            res = [gout[0], O.Scale(gout[0], scale=-1.0)]
-        elif t == 'ReduceSum':      # broadcast the [1,C] gradient down the rows
-            res = [O.Mul(O.ConstantFill(like=ws[ins[0]], value=1.0), gout[0])]
-        elif t == 'AveragedLoss':
-            res = [O.Scale(gout[0].reshape(1), 1.0 / max(ws[ins[0]].numel(), 1))]
-        elif t == 'WeightedCrossEntropyWithLogits':
-            res = [O.WeightedCrossEntropyWithLogitsGradient(ws[ins[0]], ws[ins[1]], ws[ins[2]],
-                                                            gout[0], is_mean=a.get('is_mean', False))]
-        elif t == 'CrossEntropyWithLogits':
-            res = [O.CrossEntropyWithLogitsGradient(ws[ins[0]], ws[ins[1]], gout[0],
-                                                    is_mean=a.get('is_mean', False))]
-        elif t == 'RoIFeatureBoost':
-            res = [O.RoIFeatureBoostGradient(gout[0], ws[ins[1]])]
-        elif t == 'MinEntropyLoss':
-            res = [O.MinEntropyLossGradient(ws[ins[0]], ws[ins[1]], gout[0])]
-        elif t == 'SoftmaxWithLossN':      # inputs X, T[, W]; outputs P, loss; seed = d(loss)
-            res = [O.SoftmaxWithLossNGradient(ws[ins[0]], ws[ins[1]],
-                                              ws[ins[2]] if n_in > 2 else None, ws[outs[0]],
-                                              gout[1], scale=a.get('scale', 1.0))] + [None] * (n_in - 1)
-        elif t == 'CenterLoss':     # inputs X, P, F, CF, dCF, ndCF; outputs L, D, S, picks
-            # The selection reaches the gradient half through obj.workspace, which forward and
-            # gradient share (one object per op): the `_center_picks` blob is a view of that
-            # workspace, kept in the net for fetching, not read here.
-            obj = self._stats[('CenterLoss', outs[0])]
-            res[2] = obj.gradient(ws[outs[1]], ws[outs[2]], gout[0], ws[ins[2]].shape[0],
-                                  ws[ins[3]], ws[ins[4]], ws[ins[5]])
-        else:
+        e = TABLE.get(t)
+        if e is None or e.gradient is None:
             raise NotImplementedError('gradient of ' + t)
-        for i, g in enumerate(a['_gin']):
-            if g is None or res[i] is None:
+        n_in = len(a['_gin'])
+        v = self._gather(op, ws)                # the forward op's inputs, then its outputs
+        gout = [ws[g] if g else None for g in a['_gout']]
+        res = e.gradient(self, fwd_idx, op, v[:n_in], v[n_in:], gout)
+        for i, r in enumerate(res):
+            g = a['_gin'][i]
+            if g is None or r is None:
                 continue
             if a['_accumulate'][i] and g in ws:
-                ws[g] = O.Add(ws[g], res[i]).view(res[i].shape)
+                ws[g] = O.Add(ws[g], r).view(r.shape)
             else:
-                ws[g] = res[i]
+                ws[g] = r

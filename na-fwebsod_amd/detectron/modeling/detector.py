@@ -11,6 +11,7 @@ Execution lives in detectron/core/executor.py (fused MI355X plan or op-by-op).
 import collections
 
 from detectron.core.config import cfg
+from detectron.core.op_table import cuts_flow, grad_inputs
 
 Op = collections.namedtuple('Op', ['type', 'inputs', 'outputs', 'args'])
 
@@ -45,20 +46,6 @@ class Net(object):
         return emit
 
 
-# op type -> indices of the inputs that receive a gradient (others are treated as constants)
-_GRAD_INPUTS = {
-    'FC': (0, 1, 2), 'Relu': (0,), 'Dropout': (0,), 'Softmax': (0,), 'Transpose': (0,),
-    'Mul': (0, 1), 'Add': (0, 1), 'Sub': (0, 1), 'ReduceSum': (0,), 'AveragedLoss': (0,),
-    'WeightedCrossEntropyWithLogits': (0,), 'CrossEntropyWithLogits': (0,),
-    'RoIFeatureBoost': (0,), 'MinEntropyLoss': (0,), 'SoftmaxWithLossN': (0,),
-    'CenterLoss': (2,),     # the features only (center_loss_op.cc:55-58): the centres update themselves
-    # the trainable conv body (TRAIN.FREEZE_CONV_BODY False): features only for the two poolings
-    'Conv': (0, 1, 2), 'MaxPool': (0,), 'RoIPoolF': (0,), 'RoIAlign': (0,),
-}
-_NO_GRAD = {'StopGradient', 'RoIIoU', 'Stat', 'Accuracy', 'ConstantFill', 'Shape', 'Cast',
-            'DequeueBlobs', 'RoILabel', 'RoIEntropy', 'BoxWithNMSLimit', 'RoIContext'}
-
-
 class DetectionModelHelper(object):
     def __init__(self, name='', train=False, num_classes=-1, init_params=False):
         assert num_classes > 0, 'num_classes must be > 0'
@@ -78,6 +65,7 @@ class DetectionModelHelper(object):
         self.only_build_forward_pass = False
         self.target_gpu_id = 0
         self.grad_ops = []
+        self.grad_fwd_idx = []         # parallel to grad_ops: the forward index of each one's op
         self.update_ops = []
         self.allreduce_ops = []
         self.executor = None
@@ -184,13 +172,13 @@ class DetectionModelHelper(object):
         """Reverse-mode op generation over the recorded forward ops.  `loss_gradients` maps a
         loss blob to the blob holding its gradient seed (blob.py:167-173).  Blobs consumed by
         several ops accumulate (`<name>_grad` summed), parameters shared by several FC ops
-        (the context head's fc6 / fc7 / fc8d_frame) included; StopGradient and the ops in
-        _NO_GRAD cut the flow, so nothing upstream of `roi_feat` / `conv5_3` (frozen body) or of
-        pool2 (TRAIN.FREEZE_CONV_BODY False, FREEZE_AT 2) or inside the entropy gate gets a
-        gradient op.  An FC or Conv whose input comes from such an op (or from
-        outside the net) emits no input gradient: nothing would read it."""
+        (the context head's fc6 / fc7 / fc8d_frame) included; StopGradient and the other ops that
+        core/op_table.py marks `cuts` stop the flow, so nothing upstream of `roi_feat` / `conv5_3`
+        (frozen body) or of pool2 (TRAIN.FREEZE_CONV_BODY False, FREEZE_AT 2) or inside the entropy
+        gate gets a gradient op.  An FC or Conv whose input comes from such an op
+        (or from outside the net) emits no input gradient: nothing would read it."""
         grad_of = {str(k): str(v) for k, v in loss_gradients.items()}
-        ops = []
+        ops, fwd_idx = [], []
         producer = {}           # forward index of an op -> {input blob: type of its latest producer}
         latest = {}
         for idx, op in enumerate(self.net.ops):
@@ -199,21 +187,22 @@ class DetectionModelHelper(object):
                 latest[o] = op.type
         for idx in range(len(self.net.ops) - 1, -1, -1):
             op = self.net.ops[idx]
-            if op.type in _NO_GRAD:
+            if cuts_flow(op.type):
                 for o in op.outputs:
                     grad_of.pop(o, None)
                 continue
             gouts = [grad_of.get(o) for o in op.outputs]
             if not any(gouts):
                 continue
-            if op.type not in _GRAD_INPUTS:
+            wanted = grad_inputs(op.type)
+            if wanted is None:
                 raise NotImplementedError('no gradient for op {} (blob {} needs one)'.format(
                     op.type, op.outputs[0]))
             gin = []
             for i, name in enumerate(op.inputs):
-                gin.append(name + '_grad' if i in _GRAD_INPUTS[op.type] else None)
+                gin.append(name + '_grad' if i in wanted else None)
             if op.type in ('FC', 'Conv') and (producer[idx][op.inputs[0]] is None or
-                                              producer[idx][op.inputs[0]] in _NO_GRAD):
+                                              cuts_flow(producer[idx][op.inputs[0]])):
                 # dX behind StopGradient (fc6 over a frozen body, conv3_1 over pool2): a GEMM /
                 # a convolution nobody consumes
                 gin[0] = None
@@ -225,13 +214,14 @@ class DetectionModelHelper(object):
             ops.append(Op(op.type + 'Gradient', list(op.inputs) + list(op.outputs),
                           [g for g in gin if g], dict(op.args, _gout=gouts, _gin=gin,
                                                       _accumulate=accumulate)))
+            fwd_idx.append(idx)
             for i, g in enumerate(gin):
                 if g:
                     grad_of[op.inputs[i]] = g
         for p in self.params:
             if p in grad_of:
                 self.param_to_grad[p] = grad_of[p]
-        self.grad_ops = ops
+        self.grad_ops, self.grad_fwd_idx = ops, fwd_idx
         return ops
 
     # ------------------------------------------------------------------------ lr

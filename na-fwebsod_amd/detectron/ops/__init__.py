@@ -22,6 +22,9 @@ Shape/Cast (host), AveragedLoss, Accuracy, StopGradient, Concat/Split (views).
 MaxPool takes (kernel 2, pad 0, stride 1 | 2) - the origin body, with a gradient - and (kernel 3,
 pad 1, stride 1 | 2) - the DeepLab body (VGG16.py:94-140), forward only: that body runs frozen.
 
+How the op-by-op plan calls each one (arguments, gradient rule, per-op state) is declared once, in
+detectron/core/op_table.py.
+
 Tensors are NCHW / row-major like the reference blobs.  There is no CPU fallback: CPU
 tensors raise TypeError, shape violations raise naws_hip.lib.NawsError where the reference
 op would CAFFE_ENFORCE.

@@ -181,11 +181,11 @@ def graph_grads64(model, params, fed, snapshots):
 
     params: {name: float32 tensor} the initial parameters; fed: the minibatch blobs; snapshots:
     [per forward op: the list of its outputs as the GPU run produced them].  Every op that takes
-    part in the backward (detector._GRAD_INPUTS) is restated; the discrete choices come from the
+    part in the backward (op_table.grad_inputs) is restated; the discrete choices come from the
     GPU forward as constants - ReLU masks, the max-pool selections (derived from the GPU input /
     output by the kernel's rule), RoIPoolF's argmax - so a near-tie that falls differently in
-    float32 cannot turn into an O(1) mismatch.  Every other op (the ones behind StopGradient or in
-    detector._NO_GRAD: the entropy gate, RoILabel, Stat ...) contributes its GPU output as a
+    float32 cannot turn into an O(1) mismatch.  Every other op (the ones behind StopGradient or that
+    op_table.cuts_flow: the entropy gate, RoILabel, Stat ...) contributes its GPU output as a
     constant.  SoftmaxWithLossN is restated by the surrogate whose autograd IS the reference
     gradient op (softmax_with_loss_n_op.cc:265-357 divides by the count of non-zero weights where
     the forward divides by their sum).
@@ -193,7 +193,7 @@ def graph_grads64(model, params, fed, snapshots):
     is the size of the terms an FC bias gradient sums - what its error scales with when the exact sum
     cancels (fc8d_b: the detection softmax runs over the rois, so a per-class bias moves nothing and
     its gradient is identically zero)."""
-    from detectron.modeling.detector import _GRAD_INPUTS, _NO_GRAD
+    from detectron.core.op_table import cuts_flow, grad_inputs
     env = {k: _d(torch.as_tensor(v)) for k, v in fed.items()}
     leaves = {}
     for n in model.params:
@@ -204,7 +204,7 @@ def graph_grads64(model, params, fed, snapshots):
     for op, outs_gpu in zip(model.net.ops, snapshots):
         t, a = op.type, op.args
         x = [env.get(n) for n in op.inputs]
-        if t in _NO_GRAD or t not in _GRAD_INPUTS:
+        if cuts_flow(t) or grad_inputs(t) is None:
             res = [_d(v) for v in outs_gpu]
         elif t == 'Conv':
             d = a.get('dilation', 1)

@@ -234,13 +234,13 @@ def backward_grid(dy, rois, shape, scale, sampling, variant=None):
 def graph64(model, params, fed, snapshots):
     """A recorded DetectionModelHelper graph that pools with RoIAlign, restated in torch CPU double
     the way body_grad_ref.graph_grads64 restates the RoIPoolF graphs (same rules: ReLU masks and
-    max-pool selections come from the GPU forward as constants, ops behind StopGradient or in
-    detector._NO_GRAD contribute their GPU output, SoftmaxWithLossN by the surrogate whose autograd
+    max-pool selections come from the GPU forward as constants, ops behind StopGradient or that
+    op_table.cuts_flow contribute their GPU output, SoftmaxWithLossN by the surrogate whose autograd
     is the reference gradient op), with two differences: RoIAlign is restated in the grid_sample
     form - it has no discrete choice - and the float64 blobs are returned too, so that forward
     values can be compared; a test-mode model (no losses) gets no backward.
     -> ({param: float64 gradient}, {FC bias: max_c sum_r |dY[r,c]|}, {blob: float64 tensor})."""
-    from detectron.modeling.detector import _GRAD_INPUTS, _NO_GRAD
+    from detectron.core.op_table import cuts_flow, grad_inputs
     _d = bref._d
     env = {k: _d(torch.as_tensor(v)) for k, v in fed.items()}
     leaves = {}
@@ -258,7 +258,7 @@ def graph64(model, params, fed, snapshots):
             res = list(torch.split(x[0], a['split'], dim=a.get('axis', 1)))
         elif t == 'Concat':
             res = [torch.cat(x, dim=a.get('axis', 1)), None]
-        elif t in _NO_GRAD or t not in _GRAD_INPUTS:
+        elif cuts_flow(t) or grad_inputs(t) is None:
             res = [_d(v) for v in outs_gpu]
         elif t == 'Conv':
             res = [F.conv2d(x[0], x[1], x[2], stride=1, padding=a.get('pad', 1),

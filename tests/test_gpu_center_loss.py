@@ -488,7 +488,7 @@ def test_center_loss_graph_gradient_rows(dev, webly):
     want, on_grad, off_grad = r['dF'], r['grad_on'], r['grad_off']
     model, ex = r['on']
     ws = ex.ws
-    obj = [v for k, v in ex._stats.items() if isinstance(k, tuple) and k[0] == 'CenterLoss'][0]
+    obj = [ex._state[i] for i, o in enumerate(model.net.ops) if o.type == 'CenterLoss'][0]
     own = ops.center_loss_grad(ws['D'], ws['S'], ws['loss_center_grad'].reshape(1).contiguous(), 48,
                                obj.workspace, torch.zeros_like(ws['center_feature_g']),
                                torch.zeros_like(ws['center_feature_n_u'])).cpu().numpy()

@@ -34,7 +34,8 @@ from . import head_arith
 from . import lib as L
 from . import ops
 from .planes import ALL, FcPlanes
-from .reducer import ArenaReducer, message_plan, message_slice, owner_blocks, owner_pieces
+from .reducer import ArenaReducer, message_slice, owner_pieces
+from .update import HIDDEN, UpdateSchedule
 
 VGG16_CONVS = [
     # (name, cin, cout, dilation) and pool markers
@@ -139,13 +140,7 @@ ConvLayer = collections.namedtuple('ConvLayer', 'step w b operand direct affine'
 # What a conv chain carries between layers: the activation, the int32 word of an upper bound of
 # max|x| (or None), the (mul, add) to apply to it, and whether the pool that follows is done
 ChainState = collections.namedtuple('ChainState', 'x bound affine pooled')
-# NAWS.PIPELINE_UPDATE: one launch's slice of the arena (seg: the _seg_tables of it; regions None:
-# the element-wise kernel), and an engine's tables (pieces: per FWD_PIECES; ovf: [piece ... | tail])
-UpdatePart = collections.namedtuple('UpdatePart', 'start count seg regions')
-PipeTables = collections.namedtuple('PipeTables', 'pieces bias tail ovf')
 _IDENTITY = (1.0, 0.0)
-
-HIDDEN = 4096
 
 # The side streams of every engine of a process, by (device, role): 'conv0', 'conv1', ... (one
 # chain per image) and 'update'.  HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues
@@ -247,7 +242,7 @@ class WsddnEngine(object):
         # from 4.9 GB to 4.9 / N GB for the owned rows plus 1.6 (N-1)/N GB for the planes of the
         # rows the other ranks own (their fp32 rows read once after the gather, planes written);
         # parameters bit-identical to the all-reduce route
-        # (tests/test_distributed_cpu.py, tests/test_gpu_two_ranks.py).  See _apply_update_sharded.
+        # (tests/test_distributed_cpu.py, tests/test_gpu_two_ranks.py).  See update._apply_sharded.
         self.sharded_update = bool(sharded_update)
         # NAWS.PIPELINE_UPDATE (N > 1, fp16x2 plan; None = on whenever there is an exchange): the
         # deferred update runs PIECE BY PIECE - fc6's biases, then fc6_w in two 4096-row pieces,
@@ -256,14 +251,14 @@ class WsddnEngine(object):
         # so the tail of the exchange hides under fc6 forward too instead of stalling the head
         # (2 ranks: the one xGMI link needs ~10 ms for the 958 MB, the conv body + RoIPool hide 3).
         # Same sums, same update arithmetic, same Dropout masks: parameters bit-identical to the
-        # unpipelined route (tests/test_gpu_two_ranks.py).  See _apply_update_pipelined.
+        # unpipelined route (tests/test_gpu_two_ranks.py).  See update._apply_pipelined.
         self.pipeline_update = pipeline_update
         if rank is None and process_group is not None:
             import torch.distributed as dist
             rank = dist.get_rank(process_group)
         self.rank = int(rank or 0)
-        self._shard = None
-        self._mom_synced = True
+        # when, where and by which route a step's update runs, and all the state of that (update.py)
+        self.sched = UpdateSchedule(self, lambda: side_stream(device, 'update'))
         # fc6_w's gradient (822 MB of the 958 MB all-reduce) can be reduced in row chunks while
         # the rest of its wgrad GEMM still runs.  0 = auto.  The collective has the tail of the
         # backward pass + the next iteration's parameter-free conv body + RoIPool (~5.7 ms) to
@@ -351,19 +346,9 @@ class WsddnEngine(object):
         # fp16x2 plan: each image's proposals are pooled on that image's conv stream (conv_body)
         self.ROI_POOL_ON_CHAINS = True
         self._fc8_ws = None
-        self._w6_updated = None      # the region table for the deferred kernel once fc6_w is done
         self._seg_ring = None
         self._amax5 = None
         self._streams = []
-        self._update_pending = False
-        self._update_waiting = False
-        self._upd_stream = None
-        self._upd_event = None
-        self._piece_events = None    # pipelined update: [(r0, r1, event)] of the step being joined
-        self._pipe = None            # its tables (built on first use)
-        self._pipe_state = None      # its progress while one step's parts are being queued
-        # this step's messages went out in the pipelined order / ... and backward queued the parts
-        self._pipe_sent = self._pipe_eager = self._pipe_warned = False
         self._fc = None              # FcPlanes: fc6_w / fc7_w / fc7_w^T operand planes (16-bit plans)
         self._planes_dirty = True
         # MEASUREMENT AID: NAWS_ENGINE_SET="DIRECT_MIN_TILES=100000,WINO_F4_MIN_CIN=0" overrides the
@@ -416,6 +401,16 @@ class WsddnEngine(object):
     _rm_table = property(lambda self: getattr(self._fc, 'rm_table', None))
     _sgd_regions = property(lambda self: getattr(self._fc, 'whole', None))
     _sgd_regions_rest = property(lambda self: getattr(self._fc, 'rest', None))
+    # (the schedule's state under the names others assign: bench.py resets _shard, _mom_synced and
+    # _pipe_sent around its projections, tests/test_gpu_state.py injects _upd_stream)
+    _shard = property(lambda self: self.sched.shard,
+                      lambda self, v: setattr(self.sched, 'shard', v))
+    _mom_synced = property(lambda self: self.sched.mom_synced,
+                           lambda self, v: setattr(self.sched, 'mom_synced', v))
+    _upd_stream = property(lambda self: self.sched.stream,
+                           lambda self, v: setattr(self.sched, 'stream', v))
+    _pipe_sent = property(lambda self: self.sched.step.sent,
+                          lambda self, v: setattr(self.sched.step, 'sent', v))
 
     def grad_blob(self, name):
         return self.arena.view(self.grads, name)
@@ -496,17 +491,11 @@ class WsddnEngine(object):
         one launch behind the whole exchange; sharded_update = NAWS.SHARDED_UPDATE.  All three
         routes hold bit-identical state across the ranks, so a job may change route mid-run
         (bench.py's in-run A/B, the fallback of a training job)."""
-        self.flush()
-        if self._shard_blocks() is not None:
-            self.gather_sharded_state()
-        self.pipeline_update = pipeline_update
-        self.sharded_update = bool(sharded_update)
-        self._shard, self._mom_synced = None, True
-        self._pipe_sent = False
+        self.sched.set_route(pipeline_update, sharded_update)
 
     def export_blobs(self, with_momentum=True):
         self.flush()
-        if with_momentum and not self._mom_synced:
+        if with_momentum and not self.sched.mom_synced:
             raise RuntimeError('NAWS.SHARDED_UPDATE: fc6_w momentum rows live with their owners; '
                                'call gather_sharded_state() on EVERY rank before a checkpoint')
         out = {}
@@ -604,8 +593,8 @@ class WsddnEngine(object):
         self._roi_operand = None
         self._amax5 = (torch.empty((n if per_image else 1,), device=self.device,
                                    dtype=torch.int32) if planes else None)
-        if self._update_waiting and (not per_image or not self._update_behind_heads):
-            self._launch_update(())        # no per-image conv1_1 head to put it behind
+        # a waiting update goes behind the per-image conv1_1 heads (below), or - none - out at once
+        split = self.sched.waits_for_heads(per_image and self._update_behind_heads)
         if not per_image:
             res = self._conv_chain(self.conv_layers, ChainState(data, None, _IDENTITY, False),
                                    amax_out=self._amax5).x
@@ -631,7 +620,6 @@ class WsddnEngine(object):
             self._streams.append(side_stream(self.device, 'conv%d' % len(self._streams)))
         chains = [ChainState(data[i:i + 1], None, _IDENTITY, False) for i in range(n)]
         layers = self.conv_layers
-        split = self._update_waiting and self._update_behind_heads
         if split:
             # the head of every image's chain first (conv1_1: HBM-bound, 0.06 ms alone), THEN the
             # deferred parameter update, then the rest of the chains: started together, the SGD
@@ -645,7 +633,7 @@ class WsddnEngine(object):
                 with torch.cuda.stream(st):
                     chains[i] = self._conv_chain(layers[:ua], chains[i])
                     evs.append(st.record_event())
-            self._launch_update(evs)
+            self.sched.launch(evs)
             layers = layers[ua:]
         for i in range(n):
             st = self._streams[i]
@@ -798,8 +786,8 @@ class WsddnEngine(object):
 
     def head_forward(self, roi_feat, train, both_branches=True, pieces=None):
         """roi_feat [Rt, k6] (or its operand form, written by the pooling kernel) -> H6, H7
-        [Rt, nb*4096], logits L [Rt, nb*2C].  pieces: see _join_update_for_head (the pipelined
-        update's events)."""
+        [Rt, nb*4096], logits L [Rt, nb*2C].  pieces: the pipelined update's events
+        (UpdateSchedule.join_for_head)."""
         ar = self.arith
         nb = 2 if both_branches else 1
         _w6, b6, _w7, b7, w8, b8 = self._head_views(self.params)
@@ -808,7 +796,7 @@ class WsddnEngine(object):
                            drop_ratio=self.dropout if drop else 0.0, seed=self._seed(layer))
                       for layer, b in ((6, b6), (7, b7)))
         if pieces is not None and not (ar.reports_maxima and nb == 2):
-            self._finish_pieces(pieces)      # (a caller's own plan: join the whole update first)
+            self.sched.finish_pieces(pieces)     # (a caller's own plan: join the whole update first)
             pieces = None
         W = self._fc_operands()
         # the activation operand in the plan's form (its own kernels, outside the timed launch)
@@ -867,7 +855,7 @@ class WsddnEngine(object):
                     xp, ar.rows(w6, r0, r1), h6[:, r0:r1], r0, nb * HIDDEN,
                     **dict(epi, bias=epi['bias'][r0:r1]), rowmax=rowwords[r0 // HIDDEN],
                     rowmax_seg=HIDDEN, colmax=None if colwords is None else colwords.view(-1)[r0:r1])
-        self._finish_pieces(pieces)          # fc7 / fc8 read the rest of the update
+        self.sched.finish_pieces(pieces)     # fc7 / fc8 read the rest of the update
         return h6, sc6n, sc6t
 
     def _fc8_gemm(self, a, b, trans_a, trans_b, out, epilogue=L.EPI_NONE, bias=None):
@@ -935,7 +923,7 @@ class WsddnEngine(object):
         mark('roi_pool')
         # previous iteration's all-reduce + SGD, now overlapped: joined here as a whole, or - the
         # pipelined N > 1 update - piece by piece inside the head forward
-        pieces = self._join_update_for_head()
+        pieces = self.sched.join_for_head()
         mark('join_update')
         h6, h7, lg = self.head_forward(x, train=True, pieces=pieces)
         mark('head_fwd')
@@ -1020,34 +1008,16 @@ class WsddnEngine(object):
         else:
             xt = None if amax else ops.bf16_slab_transpose(x)
         fuse = fuse_update and self._can_fuse_wgrad_update() and (pooled or not amax)
-        pipelined = self._pipelined()
-        plan = message_plan(self.arena, 2 * HIDDEN, self.allreduce_chunks, red.active, pipelined)
-        self._pipe_sent = pipelined
-        # train_step() (fuse_update): each part of the piece-by-piece update is queued on the
-        # update stream RIGHT BEHIND the message it waits for, from here, instead of after the
-        # whole backward - fc6_w, its planes and fc6's biases are not read again once the forward
-        # has run.  In queue order the update's parts then sit between the messages, so the
-        # pipeline also holds where HIP puts the update stream and the collective's stream on one
-        # hardware queue (two streams on one queue run in order; measured with ROCm's default
-        # queue count: queued after backward, every part waited behind the whole exchange).
-        eager = bool(pipelined and fuse_update and self._pipe_planes_ok())
-        if eager:
-            if self._upd_stream is None:
-                self._upd_stream = side_stream(self.device, 'update')
-            self.flush()                 # (nothing can be pending here: the head joined it)
-            with torch.cuda.stream(self._upd_stream):
-                self._pipe_begin()
-        self._pipe_eager = eager
+        # the messages of this step; pipelined train_step(): its update queued part by part behind them
+        st = self.sched.begin_backward(fuse_update)
+        plan, pipelined = st.plan, st.sent
         if pipelined:
             # fc6's bias gradients first (the first forward piece of the next iteration needs the
             # updated biases): a column sum of dZ6, known before the weight gradient
             ops.colsum(dz6, out=gb6)
             red.reduce_async(message_slice(self.arena, G, 'fc6_b', None, self.k6))
             plan = plan[1:]
-            if eager:
-                with torch.cuda.stream(self._upd_stream):
-                    self._pipe_enqueue_bias()
-        next_piece = 0
+            st.bias_sent()
         for kind, rows in plan[:-1]:
             r0, r1 = rows
             a = ar.rows(dz6t, r0, r1)
@@ -1063,10 +1033,7 @@ class WsddnEngine(object):
             else:      # each owner's rows of this chunk go to that owner only
                 for o, p0, p1 in owner_pieces(r0, r1, blocks):
                     red.reduce_to_owner_async(gw6[p0:p1].reshape(-1), o)
-            while eager and next_piece < len(self.FWD_PIECES) and self.FWD_PIECES[next_piece][1] <= r1:
-                with torch.cuda.stream(self._upd_stream):       # every chunk of this piece is out
-                    self._pipe_enqueue_piece(next_piece)
-                next_piece += 1
+            st.chunk_sent(r1)
         # 3. the small gradients (under the fc6_w exchange): fc6 db; fc7 dW = dZ7^T H6, db;
         # fc8 dW = dL^T H7, db
         if not pipelined:
@@ -1087,17 +1054,10 @@ class WsddnEngine(object):
             self._fc8_gemm(dlv, h7v, True, False, gw8)
             ops.colsum(dl, out=gb8)
         red.reduce_async(message_slice(self.arena, G, *plan[-1], self.k6))
-        if eager:
-            self._pipe_state['grads_ready'] = torch.cuda.current_stream(self.device).record_event()
-            with torch.cuda.stream(self._upd_stream):
-                self._pipe_enqueue_tail()
-                self._upd_event = self._upd_stream.record_event()
-            self._update_pending, self._update_waiting = True, False
+        st.tail_sent()
 
     def _can_fuse_wgrad_update(self):
-        return (self.fuse_wgrad_update and not self.reducer.active and self.iter_size == 1
-                and self.arith.wgrad_update and self.fused_planes
-                and self._pipe_planes_ok() and self.k6 % 256 == 0)
+        return self.sched.can_fuse_wgrad_update()
 
     def _fc6_wgrad_cut(self, a, x, xt, gw6, r0, r1, fuse):
         """fp16x2: rows r0..r1 of fc6_w's gradient (a: those rows of dZ6^T's operand; xt: x^T's, or
@@ -1137,9 +1097,7 @@ class WsddnEngine(object):
             if last:
                 fc.resplit6(w6, ALL, fc.ovf, tag)
         if last:
-            # the route is decided HERE: the deferred kernel of this step must skip fc6_w whatever
-            # the toggles say by the time it runs (the table to use travels with the flag)
-            self._w6_updated = fc.rest
+            self.sched.w6_done(fc.rest)
 
     def train_step(self, data, rois, obn_scores, labels_oh, seg=None):
         """forward_backward + sgd_step as one call.  With no gradient exchange between the two
@@ -1187,371 +1145,24 @@ class WsddnEngine(object):
         return new_lr
 
     def sgd_step(self):
-        """Queue this iteration's update.  By default it goes to a side stream: it waits there
-        for the gradient all-reduce and runs the (HBM-bound) fused SGD kernel while the main
-        stream already runs the next iteration's (MFMA-bound, parameter-free) conv body + RoIPool;
-        `flush()` — called before the head touches the parameters — joins the two streams."""
-        if self._pipe_eager:
-            self._pipe_eager = False      # train_step: backward has queued the update already
-            return
-        defer = True if self.defer_update is None else self.defer_update
-        if not defer:
-            self._apply_update()
-            return
-        main = torch.cuda.current_stream(self.device)
-        if self._upd_stream is None:
-            # an ordinary stream: a low-priority one, or one confined to a subset of the compute
-            # units, measured worse in every form (docs/history: 13.7-23 vs 13.5 ms per step)
-            self._upd_stream = side_stream(self.device, 'update')
-        self._grads_ready = main.record_event()
-        # launched by the next conv body behind conv1_1 of every image (or by flush): started at
-        # once, the SGD kernel's workgroups fill the CUs and the two conv1_1 launches at the head
-        # of the dependent chains took 0.7 ms each
-        self._update_waiting = True
-        self._update_pending = True
-
-    def _launch_update(self, after):
-        """Queue the update on its side stream, behind the gradients and the events in `after`."""
-        self._update_waiting = False
-        self._upd_stream.wait_event(self._grads_ready)
-        for e in after:
-            self._upd_stream.wait_event(e)
-        self._piece_events = None
-        with torch.cuda.stream(self._upd_stream):
-            self._apply_update()
-            self._upd_event = self._upd_stream.record_event()
+        """Queue this iteration's update (UpdateSchedule.queue: by default on a side stream, under
+        the next iteration's conv body; `flush()` - called before anything touches the parameters -
+        joins the two streams)."""
+        self.sched.queue()
 
     def flush(self):
-        if self._update_pending:
-            if self._update_waiting:
-                self._launch_update(())
-            self._update_pending = False
-            self._piece_events = None
-            torch.cuda.current_stream(self.device).wait_event(self._upd_event)
-
-    def _join_update_for_head(self):
-        """Before the head reads the parameters: join the deferred update - entirely (-> None), or,
-        when it ran piece by piece (_apply_update_pipelined), hand the pieces' events to
-        head_forward, which waits for each one right before the launch that needs it."""
-        if not self._update_pending:
-            return None
-        if self._update_waiting:
-            self._launch_update(())
-        if self._piece_events is None:
-            self.flush()
-            return None
-        pieces, self._piece_events = self._piece_events, None
-        return pieces
-
-    def _finish_pieces(self, pieces):
-        """The main stream joins what is left of a pipelined update (everything after fc6_w)."""
-        self._update_pending = False
-        torch.cuda.current_stream(self.device).wait_event(pieces['done'])
+        self.sched.flush()
 
     def _pipelined(self):
-        """True when this process's updates run piece by piece (NAWS.PIPELINE_UPDATE)."""
-        want = self.pipeline_update
-        if want is None:
-            want = True
-        on = bool(want and self.reducer.active and hasattr(self.reducer, 'wait_first')
-                  and self.arith.reports_maxima
-                  and not self.sharded_update and self.iter_size == 1 and self.k6 % 256 == 0
-                  and self.fused_planes and (self.defer_update is None or self.defer_update))
-        if on and not self._pipe_warned:
-            self._pipe_warned = True
-            if self.pg is not None and self.world_size > 1:
-                import torch.distributed as dist
-                if dist.get_backend(self.pg) != 'gloo':
-                    # ADVICE r5: per-message Work.wait() on the update stream from inside backward,
-                    # SGD pieces between collectives still in flight, fc6 forward pieces gated on
-                    # per-piece events - validated over gloo (2 and 8 ranks on one GPU) and with
-                    # one-rank RCCL only; no multi-GPU node was ever available
-                    import warnings
-                    warnings.warn('NAWS.PIPELINE_UPDATE on backend %r with %d ranks has never run '
-                                  'on hardware (validated over gloo and one-rank RCCL only); '
-                                  'NAWS.PIPELINE_UPDATE False is the fallback: the one-launch update '
-                                  'behind the whole exchange.  bench.py checks the ranks\' state '
-                                  'digests after warm-up and falls back by itself on a stall'
-                                  % (dist.get_backend(self.pg), self.world_size))
-        return on
+        return self.sched.pipelined()
 
-    def _apply_update(self):
-        if self._pipe_ready():
-            return self._apply_update_pipelined()      # (waits message by message itself)
-        # bench.py: how long this stream, with this rank's gradients complete, waits for the exchange
-        with self._timed('comm_events', on=self.reducer.active):
-            self.wait_allreduce()
-        if self._shard_blocks() is not None:
-            return self._apply_update_sharded()
-        fc, scaled = self._fc, self.arith.reports_maxima
-        rest, self._w6_updated = self._w6_updated, None
-        w6_done = rest is not None
-        # fc6_w (weights, momentum, planes) was updated by its wgrad GEMM in this step's backward:
-        # the rest MUST take the plane-writing kernel with fc6_w's region skipped, even if an A/B
-        # tool has flipped fused_planes since
-        if w6_done and (fc is None or self._sgd_regions is None or not self.arith.wgrad_update):
-            raise RuntimeError('fc6_w was updated in its wgrad epilogue but the plane state '
-                               'it belongs to is gone (engine toggles changed mid-step?)')
-        # the SGD kernel writes the planes too (a region table exists: fc is there, k6 % 256 == 0;
-        # planes marked dirty - a caller wrote through blob() - carry stale maxima: that update
-        # takes the exact route below); fp32x3 / bf16: the same kernel with their plane formats
-        writes = w6_done or (self.fused_planes and self._sgd_regions is not None
-                             and self.iter_size == 1 and not self._planes_dirty)
-        planes, planes_bf = writes and scaled, writes and not scaled
-        # fp16x2: the SGD kernel reports max|w| of every updated fc6_w / fc7_w row into the scale
-        # blocks of their operand planes, so the re-split reads the weights once (k6 % 256: a
-        # wave's 256 floats stay in one row)
-        fused = planes or (scaled and fc is not None and self.iter_size == 1 and self.k6 % 256 == 0)
-        regions = rest if w6_done else self._sgd_regions
-        w6, w7 = self._weight_views()
-        tag = self.sgd_iter_count + 1
-        with self._timed('update_events'):          # bench.py: HIP events on the update stream
-            if planes:
-                fc.begin(None if w6_done else ALL, with7=True)     # (fc6_w's half: its wgrad's)
-                self._sgd_f16x2(regions, fc.ovf, tag)
-            elif planes_bf:
-                ops.acm_sgd_update_planes(self.grads, self.momentum_buf, self.lr, self.params,
-                                          self.seg_end, self.seg_lr_mult, self.seg_wd, self.momentum, 0,
-                                          self.gpu_num, self.sgd_iter_count, regions)
-            else:
-                ops.acm_sgd_update(self.grads, self.momentum_buf, self.lr, self.params, self.acmgrad,
-                                   self.seg_end, self.seg_lr_mult, self.seg_wd, self.momentum, 0,
-                                   self.iter_size, self.gpu_num, self.sgd_iter_count,
-                                   rowmax=fc.zeroed_rowmax() if fused else None,
-                                   rm_table=self._rm_table if fused else None)
-        self.sgd_iter_count += 1
-        if planes:
-            if not w6_done:
-                fc.resplit6(w6, ALL, fc.ovf, tag)
-            fc.finish7(w7, fc.ovf, tag)
-        elif fused:                            # same stream as the update: hidden with it
-            fc.split_from_maxima(w6, w7)
-        elif planes_bf:
-            fc.convert(w7, transpose=True, out=fc.operands['w7t'])
-        elif fc is not None:
-            fc.split_all(w6, w7)
-        if fc is not None:
-            self._planes_dirty = False
-
-    def _sgd_f16x2(self, regions, ovf, tag, part=None):
-        """The plane-writing SGD kernel (fp16x2) over the whole arena, or over `part` (an
-        UpdatePart) of it; `ovf` receives `tag` when a row outgrew its bound."""
-        a, b = (0, self.arena.total) if part is None else (part.start, part.start + part.count)
-        seg = (self.seg_end, self.seg_lr_mult, self.seg_wd) if part is None else part.seg
-        ops.acm_sgd_update_f16x2(self.grads[a:b], self.momentum_buf[a:b], self.lr, self.params[a:b],
-                                 *seg, self.momentum, 0, self.gpu_num, self.sgd_iter_count, regions,
-                                 ovf, tag)
-
-    # ------------------------------------------------- NAWS.PIPELINE_UPDATE
-    FWD_PIECES = ((0, HIDDEN), (HIDDEN, 2 * HIDDEN))      # one branch each: 16 x 16 tiles of 256 x 256
-                                                          # at R = 4000 = one round of the 256 CUs
-
-    def _pipe_ready(self):
-        """The messages of this step went out in the pipelined order AND the plane-writing kernel
-        can run on them (planes valid, one hyper-parameter run per weight matrix); otherwise the
-        update waits for everything and takes the one-launch route - any message order is fine
-        for that."""
-        return (self._pipe_sent and self._pipe_planes_ok()
-                and self._upd_stream is not None
-                and torch.cuda.current_stream(self.device) == self._upd_stream)
-
-    def _pipe_planes_ok(self):
-        return self._sgd_regions is not None and not self._planes_dirty
-
-    def _seg_tables(self, start, count):
-        """(seg_end, seg_lr_mult, seg_wd) device tensors of the arena range [start, start + count),
-        ends relative to `start` (the SGD kernels take a base pointer + per-run hyper-parameters)."""
-        ends, lr_mult, wd = self._seg_host
-        first = next(i for i, e in enumerate(ends) if e > start)          # the runs that overlap it
-        last = next((i for i, e in enumerate(ends) if e >= start + count), len(ends) - 1)
-        runs = slice(first, last + 1)
-        return (torch.tensor([min(e, start + count) - start for e in ends[runs]], dtype=torch.int64,
-                             device=self.device),
-                torch.tensor(lr_mult[runs], dtype=torch.float32, device=self.device),
-                torch.tensor(wd[runs], dtype=torch.float32, device=self.device))
-
-    def _apply_update_pipelined(self):
-        """The deferred update of an N > 1 step, piece by piece (update stream).  Messages arrive
-        in the order backward handed them over: [fc6 biases][fc6_w row chunks ...][the rest].
-          1. fc6's biases (element-wise kernel on their 8192 floats);
-          2. per forward piece (FWD_PIECES: fc6_w rows of one branch): wait for the chunks that
-             cover it, run the plane-writing SGD kernel on exactly those rows (arena slice, row
-             block of the operand planes), queue the conditional exact re-split of those rows,
-             record the piece's event - the next iteration's fc6 forward launches that piece
-             behind it (head_forward) while the later messages are still on the links;
-          3. the rest (fc7_w with planes + column maxima, fc8, biases), fc7_w's transposed planes,
-             the final event.
-        Per element the arithmetic is the one-launch route's (same kernels on slices: parameters,
-        momentum, planes and scales bit-identical, tests/test_gpu_two_ranks.py); the one difference:
-        the "a row outgrew twice its previous maximum" word is kept PER PIECE, so the exact
-        re-split that answers it covers that piece's rows instead of all of fc6_w / fc7_w - the
-        other rows keep their (equally valid) bound-derived scales.
-
-        This is the form sgd_step() queues after a plain forward_backward().  train_step() queues
-        the same three parts EARLIER, from inside backward, each right behind the message it
-        waits for (_pipe_enqueue_*): fc6_w is not read again once its forward has run, so its rows
-        may be updated while the rest of backward is still computing."""
-        self._pipe_begin()
-        self._pipe_enqueue_bias()
-        for i in range(len(self.FWD_PIECES)):
-            self._pipe_enqueue_piece(i)
-        self._pipe_enqueue_tail()
-
-    def _pipe_begin(self):
-        """Start of one step's piece-by-piece update (current stream = the update stream)."""
-        if self._pipe is None:
-            def part(start, count, regions):
-                return UpdatePart(start, count, self._seg_tables(start, count), regions)
-            fc = self._fc
-            self._pipe = PipeTables([part(*fc.piece(r0, r1)) for r0, r1 in self.FWD_PIECES],
-                                    part(fc.ob, fc.o7 - fc.ob, None), part(*fc.tail()),
-                                    torch.zeros((len(self.FWD_PIECES) + 1,), device=self.device,
-                                                dtype=torch.int32))
-        self._pipe_state = dict(arrived=0, events=[], tag=self.sgd_iter_count + 1, grads_ready=None)
-
-    def _pipe_enqueue_bias(self):
-        b = self._pipe.bias
-        sl = slice(b.start, b.start + b.count)
-        self.reducer.wait_first(1)
-        ops.acm_sgd_update(self.grads[sl], self.momentum_buf[sl], self.lr, self.params[sl], None,
-                           *b.seg, self.momentum, 0, 1, self.gpu_num, self.sgd_iter_count)
-
-    def _pipe_chunks_below(self, row):
-        """How many fc6_w messages start below `row` (= must have arrived before rows < row are
-        complete)."""
-        return sum(1 for kind, rows in message_plan(self.arena, 2 * HIDDEN, self.allreduce_chunks, True, True)
-                   if kind == 'fc6_w' and rows[0] < row)
-
-    def _pipe_enqueue_piece(self, i):
-        st, fc, rows = self._pipe_state, self._fc, self.FWD_PIECES[i]
-        need = self._pipe_chunks_below(rows[1])
-        self.reducer.wait_first(need - st['arrived'])
-        st['arrived'] = need
-        ovf = self._pipe.ovf[i:i + 1]
-        fc.begin(rows, with7=False)
-        self._sgd_f16x2(self._pipe.pieces[i].regions, ovf, st['tag'], self._pipe.pieces[i])
-        fc.resplit6(self._weight_views()[0], rows, ovf, st['tag'])
-        st['events'].append((rows[0], rows[1], self._upd_stream.record_event()))
-
-    def _pipe_enqueue_tail(self):
-        st, fc, t = self._pipe_state, self._fc, self._pipe.tail
-        # bench.py (comm_events): how long this stream, with this rank's gradients complete, still
-        # waits for the exchange (`grads_ready`: the main stream behind the last gradient kernel)
-        if getattr(self, 'comm_events', None) is not None and st['grads_ready'] is not None:
-            self._upd_stream.wait_event(st['grads_ready'])
-        with self._timed('comm_events'):
-            self.reducer.wait()
-        ovf = self._pipe.ovf[-1:]
-        with self._timed('update_events'):
-            fc.begin(None, with7=True)
-            self._sgd_f16x2(t.regions, ovf, st['tag'], t)
-        self.sgd_iter_count += 1
-        fc.finish7(self._weight_views()[1], ovf, st['tag'])
-        self._planes_dirty = False
-        self._piece_events = dict(fc6=st['events'], done=self._upd_stream.record_event())
-        self._pipe_state = None
-
-    # ------------------------------------------------- NAWS.SHARDED_UPDATE
     def _shard_blocks(self):
-        """The owners' row blocks of fc6_w when the sharded update is in force, else None."""
-        if not (self.sharded_update and self.reducer.active):
-            return None
-        if self._shard is None:
-            if not self.arith.reports_maxima or self.iter_size != 1 or self.k6 % 256 != 0:
-                raise NotImplementedError('NAWS.SHARDED_UPDATE needs the fp16x2 plan, ITER_SIZE 1 '
-                                          'and a 256-multiple fc6 input')
-            blocks = owner_blocks(2 * HIDDEN, self.reducer.world_size)
-            if blocks is None:
-                raise NotImplementedError('NAWS.SHARDED_UPDATE: 8192 rows do not divide into '
-                                          '32-row multiples over %d ranks' % self.reducer.world_size)
-            self._shard = dict(blocks=blocks)
-            if self.pg is not None:
-                import warnings
-                import torch.distributed as dist
-                if dist.get_backend(self.pg) != 'gloo':
-                    # ADVICE r4: the RCCL legs of this route (per-owner dist.reduce, in-place
-                    # all_gather_into_tensor on fp32 and int32 buffers, issued from the update
-                    # stream) have never executed - no multi-GPU node was available; only the gloo
-                    # emulation (all_reduce / broadcast) has
-                    warnings.warn('NAWS.SHARDED_UPDATE on backend %r has never run on hardware '
-                                  '(validated over gloo only); check the first steps against the '
-                                  'all-reduce route' % dist.get_backend(self.pg))
-        return self._shard['blocks']
-
-    def _apply_update_sharded(self):
-        """The deferred update of a rank under NAWS.SHARDED_UPDATE (update stream):
-          1. wait for the reduces of this rank's fc6_w rows and for the small all-reduce;
-          2. the plane-writing SGD kernel over [this rank's fc6_w rows | fc7_w | fc8 | biases] - the
-             other owners' fc6_w rows are skip regions (neither read nor written);
-          3. all-gather, in place: the updated fp32 rows (822 MB / N per rank) and, per owner, the
-             rows' exact maxima, the 1/scale the owner's planes carry, and its overflow word;
-          4. one split of all 8192 rows with exactly the scales the all-reduce route would hold:
-             the owners' bound-derived ones, or - if ANY row of any owner outgrew its bound, which
-             is what the single overflow word of the all-reduce route records - the exact maxima.
-        fc7_w / fc8 / biases: as in the all-reduce route (every rank updates them)."""
-        blocks, red, fc, n6 = self._shard['blocks'], self.reducer, self._fc, 2 * HIDDEN
-        b0, b1 = blocks[self.rank]
-        nb = b1 - b0
-        self.wait_allreduce()
-        if self._planes_dirty or fc is None:
-            raise RuntimeError('sharded update: the operand planes are stale (blob() written '
-                               'through between backward and update?)')
-        sh = self._shard
-        if 'regions' not in sh:
-            if self._sgd_regions is None:
-                raise RuntimeError('the sharded update needs the plane-writing SGD kernel '
-                                   '(one hyper-parameter run over fc6_w / fc7_w)')
-            sh['regions'] = fc.shard_table(b0, b1)
-            # what travels back beside the fp32 rows: per owner [row maxima | 1/scale | overflow word]
-            sh['meta'] = torch.zeros((len(blocks), 2 * nb + 4), device=self.device, dtype=torch.int32)
-        regions, meta = sh['regions'], sh['meta']
-        max6 = fc.maxima(6)
-        tag = self.sgd_iter_count + 1
-        fc.begin((b0, b1), with7=True)
-        with self._timed('update_events'):
-            self._sgd_f16x2(regions, fc.ovf, tag)
-        self.sgd_iter_count += 1
-        self._mom_synced = len(blocks) == 1
-        # every owner's block starts from this rank's own view of those rows (what the previous
-        # gather left: right for the rows this rank does not own only until the gather below
-        # overwrites them - and what an exchange that moves no data, bench.py's projection, keeps)
-        meta[:, :nb].copy_(max6.view(len(blocks), nb))
-        meta[:, nb:2 * nb].copy_(fc.inv_scale(6).view(torch.int32).view(len(blocks), nb))
-        meta[:, 2 * nb].zero_()
-        meta[self.rank, 2 * nb:2 * nb + 1].copy_(fc.ovf)
-        w6, w7 = self._weight_views()
-        red.gather_blocks_async(w6.reshape(-1), self.rank)
-        red.gather_blocks_async(meta.view(-1), self.rank)
-        red.wait()
-        raised = (meta[:, 2 * nb] == tag).any()
-        rowmax = meta[:, :nb].reshape(n6)
-        bound_scale = (meta[:, nb:2 * nb].reshape(n6).view(torch.float32) * 16384.0).view(torch.int32)
-        max6.copy_(rowmax)
-        eff = torch.where(raised, rowmax, bound_scale)     # 1/scale = 2^(e-14)  ->  a maximum 2^e
-        fc.ovf.copy_(torch.where(raised, torch.full_like(fc.ovf, tag), fc.ovf))
-        # the rows this rank does NOT own: planes from the owners' scales (always); its own rows
-        # already carry the planes its SGD kernel wrote with exactly those scales - they are redone
-        # (from the exact maxima) only if some owner raised the overflow word (ADVICE r4: the full
-        # re-split gave back most of what the owner-only update saves)
-        if b0 > 0:
-            fc.resplit6(w6, (0, b0), rowmax=eff)
-        if b1 < n6:
-            fc.resplit6(w6, (b1, n6), rowmax=eff)
-        fc.resplit6(w6, (b0, b1), fc.ovf, tag, rowmax=eff)
-        fc.finish7(w7, fc.ovf, tag)
-        self._planes_dirty = False
+        return self.sched.shard_blocks()
 
     def gather_sharded_state(self):
-        """COLLECTIVE (every rank): bring the owners' momentum rows of fc6_w to all ranks so that
-        any rank can write a complete checkpoint.  The fp32 weights are complete on every rank
-        after each update; the momentum of a row lives with its owner only.  No-op otherwise."""
-        if self._shard_blocks() is None or self._mom_synced:
-            return
-        self.flush()
-        m6 = self.arena.span(self.momentum_buf, 'fc6_w', '_[noisy]_fc6_w')
-        self.reducer.gather_blocks_async(m6, self.rank)
-        self.reducer.wait()
-        self._mom_synced = True
+        """COLLECTIVE (every rank): the owners' momentum rows of fc6_w to all ranks (NAWS.SHARDED_UPDATE;
+        before a checkpoint).  No-op otherwise."""
+        self.sched.gather_sharded_state()
 
     # -------------------------------------------------------------- inference
     def infer(self, data, rois, obn_scores, seg=None):

@@ -27,13 +27,13 @@ def message_plan(arena, rows6, allreduce_chunks, active, pipelined=False):
     the collective: fc6_w's gradient (86 % of the bytes) in row chunks - each chunk is reduced as
     soon as its wgrad GEMM is queued - then ONE message with every other gradient (fc6 / fc7
     biases, fc7_w, fc8*: contiguous in the arena).  -> [('fc6_w', (r0, r1)), ..., ('small', None)].
-    pipelined (the N > 1 step whose fc6 forward starts piece by piece, engine._apply_update_pipelined):
-    fc6's two bias vectors (32 KB, known before the weight gradient: a column sum of dZ6) travel
+    pipelined (the N > 1 step whose fc6 forward starts piece by piece,
+    update.UpdateSchedule._apply_pipelined): fc6's two bias vectors (32 KB, known before the weight gradient: a column sum of dZ6) travel
     FIRST as a message of their own, because the first forward piece of the next iteration needs
     them, and the last message holds the rest: [('fc6_b', None), ('fc6_w', (r0, r1)), ...,
     ('rest', None)].  Same bytes, same sums.
-    The engine walks this list (engine._head_backward); tests/test_distributed_cpu.py replays it
-    on a CPU arena over gloo."""
+    update.UpdateSchedule.begin_backward builds this list and engine._head_backward walks it;
+    tests/test_distributed_cpu.py replays it on a CPU arena over gloo."""
     plan = [('fc6_w', rc) for rc in row_chunks(rows6, allreduce_chunks if active else 1)]
     if pipelined:
         return [('fc6_b', None)] + plan + [('rest', None)]

@@ -44,7 +44,7 @@ def main():
     for knob, fp in (('fused_planes=1: ', True), ('fused_planes=0: ', False)):
         eng.fused_planes = fp
         eng.update_events = []
-        t_all = timed(eng._apply_update)
+        t_all = timed(eng.sched.apply)
         ev = eng.update_events[1:]
         t_sgd = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
         eng.update_events = None

@@ -390,7 +390,7 @@ def test_unlagged_loader_failure_stops_both_ranks_in_the_same_iteration():
 
 def _pipelined_replay_worker(rank, world, port, q):
     """As _replay_worker with the PIPELINED message order (round 5: fc6's biases first, fc6_w row
-    chunks, the rest) and the update's waits in the order engine._apply_update_pipelined issues
+    chunks, the rest) and the update's waits in the order update.UpdateSchedule._apply_pipelined issues
     them: wait_first(1) for the biases, wait_first(chunks below each forward piece), wait() for
     the rest - every wait_first must leave exactly the later messages in flight."""
     sys.path.insert(0, os.path.join(ROOT, 'na-fwebsod_amd'))

@@ -112,6 +112,67 @@ int naws_nchw_to_nhwc(const float* X, int N, int C, int H, int W, float* Y, void
 int naws_nhwc_to_nchw(const float* X, int N, int H, int W, int C, float* Y, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * a-1c  ResNet18-WS conv body   ref: detectron/modeling/ResNet18.py
+ *       (add_ResNet18_conv{4,5}_body, residual_transformation) over
+ *       detectron/modeling/ResNet.py:203-256 (basic_bn_shortcut,
+ *       basic_bn_stem).  The operators are Caffe2's built-in Conv and
+ *       AffineChannel (pytorch v1.3.0 caffe2/operators); their source is
+ *       vendored neither in the reference tree nor on the build machine:
+ *       parity with a reference-executed number is UNPINNED, the arithmetic
+ *       below is the contract.  Forward only: the body runs frozen.
+ * ------------------------------------------------------------------------ */
+
+/* K of the packed operand of naws_conv2d_nhwc_fwd: kernel*kernel*Cin rounded
+ * up to a multiple of 32 (the kernel's K step); 0 for a Cin <= 0 or a kernel
+ * other than 1 / 3 / 7.  naws_conv2d_max_grid_m: the most workgroups the
+ * convolution launches along its 64-pixel tiles (the rest is grid-strided). */
+int64_t naws_conv2d_packed_k(int Cin, int kernel);
+int naws_conv2d_max_grid_m(void);
+
+/* Repack a conv weight blob [Cout,Cin,kernel,kernel] (OIHW) into the
+ * K-contiguous operand Wp [Cout][Kp], Kp = naws_conv2d_packed_k(Cin, kernel):
+ *   Wp[co][(kh*kernel + kw)*Cin + ci] = W[co][ci][kh][kw],
+ * and Wp[co][k] = 0 for kernel*kernel*Cin <= k < Kp (Cin == 3, kernel 7:
+ * K = 147, Kp = 160).  Errors as naws_conv2d_nhwc_fwd. */
+int naws_conv2d_pack_weight(const float* W_oihw, int Cout, int Cin, int kernel, float* Wp,
+                            void* stream);
+
+/* Convolution, NHWC in / out: X [N,H,W,Cin], Wp from naws_conv2d_pack_weight,
+ * bias [Cout] or NULL (no bias), Y [N,Ho,Wo,Cout] with
+ *   Ho = (H + 2*pad - dilation*(kernel-1) - 1) / stride + 1 (floor), Wo likewise,
+ *   Y[n,yo,xo,co] = bias[co] + sum over kh, kw, ci of
+ *       X[n, yo*stride - pad + kh*dilation, xo*stride - pad + kw*dilation, ci]
+ *       * W[co,ci,kh,kw],
+ * a tap outside rows 0..H-1 / columns 0..W-1 OF IMAGE n contributing 0 (it
+ * is not read), then max(., 0) when relu != 0.  fp32 throughout: every output
+ * is one k-ordered fmaf chain from 0 in the order (kh, kw, ci) on the exact
+ * fp32-input MFMA (implicit GEMM, M = N*Ho*Wo, N = Cout, K = kernel^2*Cin),
+ * the bias added last.  Any H x W: the M tiles are grid-strided.
+ * Accepted: kernel 1, 3 or 7; stride 1 or 2; dilation 1 or 2;
+ * 0 <= pad <= dilation*(kernel-1); Cout % 32 == 0; Cin == 3 or Cin % 32 == 0.
+ * Errors, all before any launch, in this order: a non-positive dim -> SHAPE;
+ * kernel / stride / dilation / pad outside the above -> ARG; a channel count
+ * outside the rule -> UNSUPPORTED; Ho or Wo < 1 -> SHAPE; X, Wp or Y missing
+ * -> NULL; X, Wp or Y not 16-byte aligned -> ARG.  The forms the ResNet18
+ * body uses: 7x7 / s2 / p3 with Cin 3; 3x3 / s2 / p1; 1x1 / s2 / p0;
+ * 1x1 / s1 / p0 (3x3 / s1 / pad == dilation is served by
+ * naws_conv3x3_nhwc_fwd above and accepted here too). */
+int naws_conv2d_nhwc_fwd(const float* X, const float* Wp, const float* bias, int N, int H, int W,
+                         int Cin, int Cout, int kernel, int stride, int pad, int dilation,
+                         int relu, float* Y, void* stream);
+
+/* AffineChannel (the frozen BatchNorm of a fine-tuned ResNet), NCHW - the
+ * layout the op-by-op plan hands between ops: X, Y [N,C,HW], scale, shift [C],
+ *   Y[n,c,i] = X[n,c,i] * scale[c] + shift[c], then max(., 0) when relu != 0.
+ * The product and the sum round separately (no FMA contraction): bit-equal
+ * to a float32 multiply followed by a float32 add.  In place (Y == X) is
+ * allowed; X and Y must not overlap otherwise.  HW need not be a multiple of
+ * 4; tensors off 16 bytes are handled (element by element).  Errors before
+ * any launch: a non-positive dim -> SHAPE; a missing pointer -> NULL. */
+int naws_affine_channel_fwd(const float* X, const float* scale, const float* shift, int N, int C,
+                            int64_t HW, int relu, float* Y, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * a-1b  Backward of the conv body (TRAIN.FREEZE_CONV_BODY False, op-by-op
  *       plan)   ref: Caffe2 ConvGradient / MaxPoolGradient (pytorch v1.3.0
  *       caffe2/operators/conv_op_impl.h, pool_gradient_op.cc) as

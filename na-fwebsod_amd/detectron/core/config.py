@@ -116,6 +116,15 @@ def _defaults():
             'PCL': False, 'CMIL': False, 'MEAN_LOSS': False, 'USE_DISTORTION': True,
             'SATURATION': 1.5, 'EXPOSURE': 1.5, 'USE_CROP': True, 'CROP': 0.9, 'DILATION': 1,
             'MIN_ENTROPY_LOSS': False,
+            # the two hidden widths of wsl_heads.add_ResNet_roi_2fc_head ([]: FAST_RCNN.MLP_HEAD_DIM)
+            'MLP_HEAD_DIM': [],
+        },
+        # the ResNet bodies (ref: config.py RESNETS); modeling/ResNet18.py builds
+        # residual_transformation blocks over the bn stem / shortcut at NUM_GROUPS 1 and refuses the rest
+        'RESNETS': {
+            'NUM_GROUPS': 1, 'WIDTH_PER_GROUP': 64, 'STRIDE_1X1': True,
+            'TRANS_FUNC': 'bottleneck_transformation', 'STEM_FUNC': 'basic_bn_stem',
+            'SHORTCUT_FUNC': 'basic_bn_shortcut', 'RES5_DILATION': 1,
         },
         'WEBLY': {
             'WEBLY_ON': False, 'ENTROPY': False, 'MINING': False, 'BAGGING_MIXUP': False,

@@ -54,15 +54,28 @@ def _binary(name, grad_inputs=None, gradient=None):
 
 _CONV = ('kernel', 'pad', 'stride', 'dilation')
 
+
+def _conv(op):
+    """A Conv op without a pad argument has none (the operator's default, which the 1x1 shortcuts
+    of the ResNet builders rely on), not O.Conv's keyword default of 1."""
+    return dict({'pad': 0}, **_kw(op, *_CONV))
+
 TABLE = {
     # ------------------------------------------------------------------ conv body
-    'Conv': _op(lambda ex, i, op, x: (O.Conv(x[0], x[1], x[2], **_kw(op, *_CONV)),), 3, (0, 1, 2),
+    # inputs X, W[, b]: a Conv the builders make with no_bias carries two
+    'Conv': _op(lambda ex, i, op, x: (O.Conv(x[0], x[1], x[2] if len(x) > 2 else None,
+                                             **_conv(op)),), 3, (0, 1, 2),
                 lambda ex, i, op, x, y, g: _dx_first(*O.ConvGradient(
-                    x[0], x[1], g[0], need_dx=_need_dx(op), **_kw(op, *_CONV)))),
+                    x[0], x[1], g[0], need_dx=_need_dx(op), **_conv(op)))),
     'Relu': _op(lambda ex, i, op, x: (O.Relu(x[0]),), 1, (0,),
                 lambda ex, i, op, x, y, g: [O.ReluGradient(y[0], g[0])]),
     'MaxPool': _op(lambda ex, i, op, x: (O.MaxPool(x[0], **_pool(op)),), 1, (0,),
                    lambda ex, i, op, x, y, g: [O.MaxPoolGradient(x[0], y[0], g[0], **_pool(op))]),
+    # the ResNet bodies (forward only: they run frozen).  inputs X, s, b; in place when the builder
+    # names the input as the output
+    'AffineChannel': _op(lambda ex, i, op, x: (O.AffineChannel(
+        x[0], x[1], x[2], out=x[0] if op.outputs[0] == op.inputs[0] else None),), 3),
+    'Sum': _op(lambda ex, i, op, x: (O.Sum(x[0], x[1]),), 2),
     'StopGradient': _op(lambda ex, i, op, x: (x[0],), 1, cuts=True),
     'DequeueBlobs': _op(None, 0, cuts=True),     # the loader's op: named by a builder, never run
     # -------------------------------------------------------------------- RoI ops

@@ -2,8 +2,8 @@
 generates its backward ops — the role Caffe2's CNNModelHelper + core.Net + AddGradientOperators
 play for the reference (detectron/modeling/detector.py:43-586).
 
-Same builder-facing surface for the hot path: `model.Conv/Relu/MaxPool/FC/Dropout/Softmax/
-Transpose/StopGradient/Accuracy/RoIFeatureTransform`, `model.net.<AnyOp>(inputs, outputs,
+Same builder-facing surface for the hot path: `model.Conv/AffineChannel/ConvAffine/Relu/MaxPool/
+FC/Dropout/Softmax/Transpose/StopGradient/Accuracy/RoIFeatureTransform`, `model.net.<AnyOp>(inputs, outputs,
 **args)`, `model.param_init_net.ConstantFill`, `AddLosses/AddMetrics/TrainableParams`,
 `UpdateWorkspaceLr`.  One process drives one GPU, so blob names carry no `gpu_i/` scope.
 Execution lives in detectron/core/executor.py (fused MI355X plan or op-by-op).
@@ -95,12 +95,34 @@ class DetectionModelHelper(object):
 
     # --------------------------------------------------------------- layer helpers
     def Conv(self, blob_in, blob_out, dim_in, dim_out, kernel, weight_init=None, bias_init=None,
-             **kwargs):
+             no_bias=0, group=1, **kwargs):
+        """stride / pad / dilation ride in kwargs to the op.  no_bias (the ResNet builders, whose
+        AffineChannel carries the shift): no `<out>_b` parameter, a two-input op."""
+        if group != 1:
+            raise NotImplementedError('Conv group: {} is not on the hot path (RESNETS.NUM_GROUPS '
+                                      'must be 1)'.format(group))
         w = self._create_param(blob_out + '_w', (dim_out, dim_in, kernel, kernel),
                                weight_init or ('XavierFill', {}), False)
+        if no_bias:
+            return self.net.add('Conv', [blob_in, w], [blob_out], dict(kwargs, kernel=kernel))
         b = self._create_param(blob_out + '_b', (dim_out,),
                                bias_init or ('ConstantFill', {'value': 0.0}), True)
         return self.net.add('Conv', [blob_in, w, b], [blob_out], dict(kwargs, kernel=kernel))
+
+    def AffineChannel(self, blob_in, blob_out, dim, inplace=False):
+        """ref: detector.py:81-105: the per-channel affine that stands for BatchNorm in a
+        fine-tuned ResNet; `<out>_s` starts at 1, `<out>_b` at 0."""
+        s = self._create_param(blob_out + '_s', (dim,), ('ConstantFill', {'value': 1.0}), False)
+        b = self._create_param(blob_out + '_b', (dim,), ('ConstantFill', {'value': 0.0}), True)
+        return self.net.add('AffineChannel', [blob_in, s, b], [blob_in if inplace else blob_out], {})
+
+    def ConvAffine(self, blob_in, prefix, dim_in, dim_out, kernel, stride, pad, group=1, dilation=1,
+                   weight_init=None, bias_init=None, suffix='_bn', inplace=False):
+        """ref: detector.py:428-456: a bias-free Conv followed by AffineChannel."""
+        conv_blob = self.Conv(blob_in, prefix, dim_in, dim_out, kernel, stride=stride, pad=pad,
+                              group=group, dilation=dilation, weight_init=weight_init,
+                              bias_init=bias_init, no_bias=1)
+        return self.AffineChannel(conv_blob, prefix + suffix, dim=dim_out, inplace=inplace)
 
     def FC(self, blob_in, blob_out, dim_in, dim_out, weight_init=None, bias_init=None, **kwargs):
         w = self._create_param(blob_out + '_w', (dim_out, dim_in),

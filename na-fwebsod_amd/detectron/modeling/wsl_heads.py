@@ -4,7 +4,7 @@ add_VGG16_roi_2fc_head (:654-681), DropoutIfTraining (:1259-1267); and, one cfg 
 (WSL.OICR): add_wsl_oicr_outputs (:134-156), add_wsl_losses (:375-458),
 add_oicr_losses (:512-560); (WSL.CONTEXT, the ContextLocNet contrastive head):
 add_wsl_context_outputs (:185-209), add_VGG16_roi_context_2fc_head (:684-766); (WSL.CENTER_LOSS, the multi-centre feature loss on
-drop7): add_center_loss (:230-276).  The PCL / CMIL / CSC heads of that file are other WSOD
+drop7): add_center_loss (:230-276); (the ResNet18 bodies) add_ResNet_roi_{0,1,2}fc_head (:769-895).  The PCL / CMIL / CSC heads of that file are other WSOD
 methods (cfg switches that core/config.py rejects)."""
 from detectron.core.config import cfg
 from detectron.utils.c2 import const_fill, gauss_fill
@@ -169,6 +169,68 @@ def add_VGG16_roi_2fc_head(model, blob_in, dim_in, spatial_scale, prefix=''):
     out = _two_fc(model, feat, prefix + 'fc6', prefix + 'drop6', prefix + 'fc7', prefix + 'drop7',
                   dim_in * roi_size * roi_size)
     return out, 4096
+
+
+def _resnet_roi_feat(model, blob_in, spatial_scale, prefix):
+    roi_size = cfg.FAST_RCNN.ROI_XFORM_RESOLUTION
+    feat = model.RoIFeatureTransform(
+        blob_in, prefix + 'roi_feat', blob_rois=prefix + 'rois',
+        method=cfg.FAST_RCNN.ROI_XFORM_METHOD, resolution=roi_size,
+        sampling_ratio=cfg.FAST_RCNN.ROI_XFORM_SAMPLING_RATIO, spatial_scale=spatial_scale)
+    feat = model.net.RoIFeatureBoost([feat, prefix + 'obn_scores'], feat)
+    if cfg.TRAIN.FREEZE_CONV_BODY:
+        feat = model.StopGradient(feat, feat)
+    return feat, roi_size
+
+
+def _no_resnet_context(name):
+    if cfg.WSL.CONTEXT:
+        raise NotImplementedError('WSL.CONTEXT with {} is not on the hot path: the contextual head '
+                                  'is built over add_VGG16_roi_2fc_head only'.format(name))
+
+
+def add_ResNet_roi_context_0fc_head(model, blob_in, dim_in, spatial_scale, prefix=''):
+    """wsl_heads.py:800-830: not built."""
+    raise NotImplementedError('WSL.CONTEXT: add_ResNet_roi_context_0fc_head is not on the hot path')
+
+
+def add_ResNet_roi_context_2fc_head(model, blob_in, dim_in, spatial_scale, prefix=''):
+    """wsl_heads.py:898-: not built."""
+    raise NotImplementedError('WSL.CONTEXT: add_ResNet_roi_context_2fc_head is not on the hot path')
+
+
+def add_ResNet_roi_0fc_head(model, blob_in, dim_in, spatial_scale, prefix=''):
+    """wsl_heads.py:769-797: the boosted roi features themselves, no hidden layer."""
+    _no_resnet_context('add_ResNet_roi_0fc_head')
+    feat, roi_size = _resnet_roi_feat(model, blob_in, spatial_scale, prefix)
+    return feat, dim_in * roi_size * roi_size
+
+
+def add_ResNet_roi_1fc_head(model, blob_in, dim_in, spatial_scale, prefix=''):
+    """wsl_heads.py:833-857: one hidden layer of FAST_RCNN.MLP_HEAD_DIM units."""
+    _no_resnet_context('add_ResNet_roi_1fc_head')
+    hidden_dim = cfg.FAST_RCNN.MLP_HEAD_DIM
+    feat, roi_size = _resnet_roi_feat(model, blob_in, spatial_scale, prefix)
+    blob = model.FC(feat, prefix + 'fc6', dim_in * roi_size * roi_size, hidden_dim)
+    blob = model.Relu(blob, prefix + 'fc6')
+    return DropoutIfTraining(model, blob, prefix + 'drop6', 0.5), hidden_dim
+
+
+def add_ResNet_roi_2fc_head(model, blob_in, dim_in, spatial_scale, prefix=''):
+    """wsl_heads.py:860-895: two hidden layers, WSL.MLP_HEAD_DIM's two widths when it holds two,
+    FAST_RCNN.MLP_HEAD_DIM for both otherwise."""
+    _no_resnet_context('add_ResNet_roi_2fc_head')
+    if len(cfg.WSL.MLP_HEAD_DIM) == 2:
+        dim6, dim7 = cfg.WSL.MLP_HEAD_DIM
+    else:
+        dim6 = dim7 = cfg.FAST_RCNN.MLP_HEAD_DIM
+    feat, roi_size = _resnet_roi_feat(model, blob_in, spatial_scale, prefix)
+    blob = model.FC(feat, prefix + 'fc6', dim_in * roi_size * roi_size, dim6)
+    blob = model.Relu(blob, prefix + 'fc6')
+    blob = DropoutIfTraining(model, blob, prefix + 'drop6', 0.5)
+    blob = model.FC(blob, prefix + 'fc7', dim6, dim7)
+    blob = model.Relu(blob, prefix + 'fc7')
+    return DropoutIfTraining(model, blob, prefix + 'drop7', 0.5), dim7
 
 
 def _two_fc_shared(model, blob, prefix, suffix):

@@ -16,8 +16,9 @@ Custom ops (reference detectron/ops/*):
   CenterLoss(+Gradient)                   center_loss_op.cu:33-568        (WSL.CENTER_LOSS)
   ACMWeightDecayMomentumSGDUpdate         acm_weightdecay_momentum_sgd_op.h:48-112
 Caffe2 built-ins used by the path (pytorch v1.3.0 caffe2/operators, restated): RoIPoolF
-(+Gradient), RoIAlign(+Gradient), Conv(+Gradient), Relu, MaxPool(+Gradient), FC, Dropout, Softmax, Transpose,
-Add/Sub/Mul/Div (numpy-style broadcast), ReduceSum, Log, Scale, ReplaceNaN, MatMul, LeakyRelu, Clip, ConstantFill,
+(+Gradient), RoIAlign(+Gradient), Conv(+Gradient), AffineChannel, Relu, MaxPool(+Gradient), FC, Dropout,
+Softmax, Transpose, Add/Sub/Mul/Div (numpy-style broadcast), Sum (two equal shapes), ReduceSum, Log, Scale,
+ReplaceNaN, MatMul, LeakyRelu, Clip, ConstantFill,
 Shape/Cast (host), AveragedLoss, Accuracy, StopGradient, Concat/Split (views).
 MaxPool takes (kernel 2, pad 0, stride 1 | 2) - the origin body, with a gradient - and (kernel 3,
 pad 1, stride 1 | 2) - the DeepLab body (VGG16.py:94-140), forward only: that body runs frozen.
@@ -391,17 +392,30 @@ class ACMWeightDecayMomentumSGDUpdate(object):
 
 
 # ------------------------------------------------------------------- Caffe2 built-ins
-def Conv(X, W, b, kernel=3, pad=1, stride=1, dilation=1, relu=False):
-    """NCHW 3x3 stride-1 convolution (the only shape on the path).  `relu` fuses the
-    following in-place Relu."""
-    if kernel != 3 or stride != 1 or pad != dilation:
-        raise NawsError('Conv', _L.ERR_UNSUPPORTED)
+def Conv(X, W, b=None, kernel=3, pad=1, stride=1, dilation=1, relu=False):
+    """NCHW convolution; b None: no bias (the `no_bias` Conv of the ResNet builders).  `relu` fuses
+    the following in-place Relu.  3x3 / stride 1 / pad == dilation - every VGG-16 layer - keeps its
+    own kernels; the other forms (kernel 1 / 3 / 7, stride 1 / 2, dilation 1 / 2: the ResNet18
+    body's 7x7 / s2 stem, 3x3 / s2 and 1x1 convs) go to naws_conv2d_nhwc_fwd, whose arithmetic is
+    stated in include/naws.h (a-1c)."""
     cin = X.shape[1]
-    if cin == 3:
-        y = _k.conv3x3_c3_nchw_to_nhwc(X, W, b, relu)
-    else:
-        y = _k.conv3x3_nhwc(_k.nchw_to_nhwc(X), _k.conv3x3_pack_weight(W), b, dilation, relu)
+    if kernel == 3 and stride == 1 and pad == dilation and (cin == 3 or cin % 32 == 0):
+        if cin == 3:
+            y = _k.conv3x3_c3_nchw_to_nhwc(X, W, b, relu)
+        else:
+            y = _k.conv3x3_nhwc(_k.nchw_to_nhwc(X), _k.conv3x3_pack_weight(W), b, dilation, relu)
+        return _k.nhwc_to_nchw(y)
+    if tuple(W.shape[1:]) != (cin, kernel, kernel):
+        raise NawsError('Conv', _L.ERR_SHAPE)
+    y = _k.conv2d_nhwc(_k.nchw_to_nhwc(X), _k.conv2d_pack_weight(W), b, kernel, stride, pad,
+                       dilation, relu)
     return _k.nhwc_to_nchw(y)
+
+
+def AffineChannel(X, S, B, relu=False, out=None):
+    """Caffe2 AffineChannel (NCHW): Y = X * S[c] + B[c], the frozen BatchNorm of the ResNet
+    builders (detector.py:81-105); out may be X (the builders' inplace form)."""
+    return _k.affine_channel(X, S, B, relu, out=out)
 
 
 def ConvGradient(X, W, dY, kernel=3, pad=1, stride=1, dilation=1, need_dx=True):
@@ -527,6 +541,13 @@ def _bin(op, A, B):
 
 def Add(A, B, broadcast=True):
     return _bin(_L.BIN_ADD, A, B)
+
+
+def Sum(A, B):
+    """Caffe2 Sum as the residual blocks use it (ResNet18.py:161-164): two blobs of one shape."""
+    if A.shape != B.shape:
+        raise NawsError('Sum', _L.ERR_SHAPE)
+    return Add(A.reshape(A.shape[0], -1), B.reshape(B.shape[0], -1)).view(A.shape)
 
 
 def Sub(A, B, broadcast=True):

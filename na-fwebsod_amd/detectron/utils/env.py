@@ -70,11 +70,20 @@ def yaml_dump(cfg_node, stream=None, reference_format=False):
     `!!python/object/new:detectron.utils.collections.AttrDict {dictitems, state}`); ndarray /
     tuple values go out as lists, which the reference's type check converts back
     (config.py:1393-1420); the NAWS subtree - options of this implementation, unknown keys to
-    the reference's merge - is left out."""
+    the reference's merge - is left out.  So are the ResNet keys (the RESNETS subtree,
+    WSL.MLP_HEAD_DIM) while they hold the reference's own defaults: the reader then keeps exactly
+    those values, and a run over a VGG-16 body writes the text it always wrote; a run that sets one
+    of them dumps it."""
     tree = _plain(cfg_node)
     if not reference_format:
         return yaml.dump(tree, stream=stream)
     tree = {k: v for k, v in tree.items() if k != 'NAWS'}
+    from detectron.core.config import _defaults
+    ref = _plain(_defaults())
+    if tree.get('RESNETS') == ref['RESNETS']:
+        del tree['RESNETS']
+    if 'WSL' in tree and tree['WSL'].get('MLP_HEAD_DIM') == ref['WSL']['MLP_HEAD_DIM']:
+        tree['WSL'] = {k: v for k, v in tree['WSL'].items() if k != 'MLP_HEAD_DIM'}
     return yaml.dump(_as_ref_nodes(tree), stream=stream, Dumper=_RefDumper)
 
 

@@ -39,6 +39,9 @@ PROTOTYPES = {
     'naws_maxpool2x2_nhwc_fwd': [p, i32, i32, i32, i32, i32, p, p],
     'naws_maxpool2x2_nhwc_bwd': [p, p, p, i32, i32, i32, i32, i32, p, p],
     'naws_maxpool3x3_nhwc_fwd': [p, i32, i32, i32, i32, i32, p, p],
+    'naws_conv2d_pack_weight': [p, i32, i32, i32, p, p],
+    'naws_conv2d_nhwc_fwd': [p, p, p, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, p, p],
+    'naws_affine_channel_fwd': [p, p, p, i32, i32, i64, i32, p, p],
     'naws_conv3x3_dgrad_pack_weight': [p, i32, i32, p, p],
     'naws_conv3x3_nhwc_wgrad': [p, p, i32, i32, i32, i32, i32, i32, p, p, p, p],
     'naws_roi_pool_f_bwd': [p, p, p, i32, i32, i32, i32, i32, i32, i32, i32, p, p],
@@ -162,6 +165,8 @@ SPECIAL = {
     'naws_last_hip_error': ([], i32),
     'naws_entropy_gate_workspace_floats': ([i32, i32, i32, i32], i64),
     'naws_winograd_workspace_floats': ([i32, i32, i32, i32, i32, i32], i64),
+    'naws_conv2d_packed_k': ([i32, i32], i64),
+    'naws_conv2d_max_grid_m': ([], i32),
     'naws_nms_workspace_bytes': ([i32, i32], i64),
     'naws_roi_label_workspace_bytes': ([i32, i32, i32], i64),
     'naws_softmax_with_loss_n_workspace_floats': ([i32], i64),

@@ -132,6 +132,68 @@ def maxpool3x3_nhwc(x, stride, out=None):
     return y
 
 
+def conv2d_pack_weight(w_oihw):
+    """OIHW [Cout, Cin, k, k] -> the operand [Cout, Kp] of conv2d_nhwc: k-contiguous in the order
+    (kh, kw, ci), zero-padded from k * k * Cin to Kp = naws_conv2d_packed_k (a multiple of 32)."""
+    _chk(w_oihw, 'w')
+    cout, cin, kernel = w_oihw.shape[:3]
+    if w_oihw.dim() != 4 or w_oihw.shape[3] != kernel:
+        raise L.NawsError('naws_conv2d_pack_weight', L.ERR_SHAPE)
+    kp = max(int(L.load().naws_conv2d_packed_k(cin, kernel)), 4)
+    wp = torch.empty((cout, kp), device=w_oihw.device, dtype=_f32)
+    L.call('naws_conv2d_pack_weight', w_oihw.data_ptr(), cout, cin, kernel, wp.data_ptr(), _stream())
+    return wp
+
+
+def conv2d_out_size(h, w, kernel, stride, pad, dilation):
+    """The floor rule of naws_conv2d_nhwc_fwd."""
+    span = dilation * (kernel - 1) + 1
+    return (h + 2 * pad - span) // stride + 1, (w + 2 * pad - span) // stride + 1
+
+
+def conv2d_nhwc(x, w_packed, bias, kernel, stride=1, pad=0, dilation=1, relu=False, out=None):
+    """Convolution of kernel 1 / 3 / 7, stride 1 / 2, dilation 1 / 2 (the ResNet18 body's forms):
+    x [n, h, w, cin] NHWC, w_packed from conv2d_pack_weight, bias [cout] or None -> [n, ho, wo, cout]."""
+    _chk(x, 'x'); _chk(w_packed, 'w_packed')
+    if bias is not None:
+        _chk(bias, 'bias')
+    n, h, w, cin = x.shape
+    cout = w_packed.shape[0]
+    if stride not in (1, 2) or dilation not in (1, 2) or kernel not in (1, 3, 7):
+        raise L.NawsError('naws_conv2d_nhwc_fwd', L.ERR_ARG)
+    if w_packed.dim() != 2 or w_packed.shape[1] != L.load().naws_conv2d_packed_k(cin, kernel) or \
+            (bias is not None and bias.numel() != cout):
+        raise L.NawsError('naws_conv2d_nhwc_fwd', L.ERR_SHAPE)
+    ho, wo = conv2d_out_size(h, w, kernel, stride, pad, dilation)
+    if ho < 1 or wo < 1:
+        raise L.NawsError('naws_conv2d_nhwc_fwd', L.ERR_SHAPE)
+    if out is not None:
+        _chk(out, 'out')
+        if tuple(out.shape) != (n, ho, wo, cout):
+            raise L.NawsError('naws_conv2d_nhwc_fwd', L.ERR_SHAPE)
+    y = out if out is not None else torch.empty((n, ho, wo, cout), device=x.device, dtype=_f32)
+    L.call('naws_conv2d_nhwc_fwd', x.data_ptr(), w_packed.data_ptr(), _ptr(bias), n, h, w, cin, cout,
+           kernel, stride, pad, dilation, int(relu), y.data_ptr(), _stream())
+    return y
+
+
+def affine_channel(x, scale, shift, relu=False, out=None):
+    """y[n, c, ...] = x[n, c, ...] * scale[c] + shift[c] (product and sum rounded separately) on an
+    NCHW tensor; out may be x itself (in place)."""
+    _chk(x, 'x'); _chk(scale, 'scale'); _chk(shift, 'shift')
+    if x.dim() < 2 or scale.numel() != x.shape[1] or shift.numel() != x.shape[1]:
+        raise L.NawsError('naws_affine_channel_fwd', L.ERR_SHAPE)
+    if out is not None:
+        _chk(out, 'out')
+        if out.shape != x.shape:
+            raise L.NawsError('naws_affine_channel_fwd', L.ERR_SHAPE)
+    y = out if out is not None else torch.empty_like(x)
+    n, c = x.shape[:2]
+    L.call('naws_affine_channel_fwd', x.data_ptr(), scale.data_ptr(), shift.data_ptr(), n, c,
+           x.numel() // max(n * c, 1), int(relu), y.data_ptr(), _stream())
+    return y
+
+
 def nchw_to_nhwc(x):
     _chk(x, 'x')
     n, c, h, w = x.shape

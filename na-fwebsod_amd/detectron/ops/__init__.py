@@ -397,16 +397,23 @@ def Conv(X, W, b=None, kernel=3, pad=1, stride=1, dilation=1, relu=False):
     the following in-place Relu.  3x3 / stride 1 / pad == dilation - every VGG-16 layer - keeps its
     own kernels; the other forms (kernel 1 / 3 / 7, stride 1 / 2, dilation 1 / 2: the ResNet18
     body's 7x7 / s2 stem, 3x3 / s2 and 1x1 convs) go to naws_conv2d_nhwc_fwd, whose arithmetic is
-    stated in include/naws.h (a-1c)."""
+    stated in include/naws.h (a-1c).  The 3-channel kernel of conv1_1 has no dilation argument: it
+    serves dilation 1 only, a dilated 3-channel conv goes to naws_conv2d_nhwc_fwd.  W must be
+    [Cout, Cin, kernel, kernel] on every route (ERR_SHAPE)."""
     cin = X.shape[1]
-    if kernel == 3 and stride == 1 and pad == dilation and (cin == 3 or cin % 32 == 0):
+    if W.dim() != 4 or tuple(W.shape[1:]) != (cin, kernel, kernel):
+        raise NawsError('Conv', _L.ERR_SHAPE)
+    if kernel == 3 and stride == 1 and pad == dilation and \
+            ((cin == 3 and dilation == 1) or cin % 32 == 0):
         if cin == 3:
             y = _k.conv3x3_c3_nchw_to_nhwc(X, W, b, relu)
         else:
+            if b is None and relu:
+                # naws_conv3x3_nhwc_fwd fuses the ReLU into its bias epilogue only: a zero bias
+                # (conv + 0 is the conv, bit for bit) keeps this route and its Cout % 4 rule
+                b = torch.zeros((W.shape[0],), device=X.device, dtype=torch.float32)
             y = _k.conv3x3_nhwc(_k.nchw_to_nhwc(X), _k.conv3x3_pack_weight(W), b, dilation, relu)
         return _k.nhwc_to_nchw(y)
-    if tuple(W.shape[1:]) != (cin, kernel, kernel):
-        raise NawsError('Conv', _L.ERR_SHAPE)
     y = _k.conv2d_nhwc(_k.nchw_to_nhwc(X), _k.conv2d_pack_weight(W), b, kernel, stride, pad,
                        dilation, relu)
     return _k.nhwc_to_nchw(y)

@@ -110,6 +110,84 @@ def test_op_layer_routes(dev):
             O.Conv(x.to(dev), torch.zeros((128, 64, kw['kernel'], kw['kernel']), device=dev), None, **kw)
 
 
+def _int_inputs(n, cin, cout, k, h, w, seed):
+    """Integers (x, weight in [-4, 4], bias in [-64, 64]): every partial sum of a convolution of
+    K <= 49 * 32 stays an integer below 2^24, so fp32 in any order gives the float64 result."""
+    rng = np.random.default_rng(seed)
+    x = torch.from_numpy(rng.integers(-4, 5, (n, cin, h, w)).astype(np.float32))
+    wt = torch.from_numpy(rng.integers(-4, 5, (cout, cin, k, k)).astype(np.float32))
+    b = torch.from_numpy(rng.integers(-64, 65, (cout,)).astype(np.float32))
+    return x, wt, b
+
+
+@pytest.mark.parametrize('k,s,d', [(k, s, d) for k in (1, 3, 7) for s in (1, 2) for d in (1, 2)])
+def test_op_conv_domain_exact(dev, k, s, d):
+    """O.Conv, NCHW, N = 2 on 9 x 11 (15 x 17 where the window is wider than 9): kernel x stride x
+    dilation at the natural pad dilation * (kernel - 1) / 2 and at pad 0, Cin 3 and 32, bias or None,
+    ReLU or not - both routes and the seam between them - EQUAL to F.conv2d in float64 (integer
+    inputs).  Every row is run before the failures are reported."""
+    import detectron.ops as O
+    span, failed = d * (k - 1) + 1, []
+    for p in sorted({d * (k - 1) // 2, 0}):
+        h, w = (9, 11) if span - 2 * p <= 9 else (span - 2 * p + 2, span - 2 * p + 4)
+        for cin in (3, 32):
+            x, wt, b = _int_inputs(2, cin, 32, k, h, w, seed=1000 * k + 100 * s + 10 * d + p + cin)
+            pre = F.conv2d(x.double(), wt.double(), None, s, p, d)
+            for bias in (b, None):
+                y = pre if bias is None else pre + b.double().view(1, -1, 1, 1)
+                assert float(y.abs().max()) < 2 ** 24
+                for relu in (False, True):
+                    want = y.relu() if relu else y
+                    assert not relu or (bool((want == 0).any()) and bool((want > 0).any()))
+                    row = 'cin %d kernel %d stride %d pad %d dilation %d bias %s relu %s' % (
+                        cin, k, s, p, d, bias is not None, relu)
+                    try:
+                        got = O.Conv(x.to(dev), wt.to(dev), None if bias is None else bias.to(dev),
+                                     kernel=k, pad=p, stride=s, dilation=d, relu=relu)
+                    except O.NawsError as e:
+                        failed.append('%s: %s' % (row, e))
+                        continue
+                    assert tuple(got.shape) == tuple(want.shape), row
+                    if not torch.equal(got.double().cpu(), want):
+                        failed.append('%s: %d of %d values differ' % (
+                            row, int((got.double().cpu() != want).sum()), want.numel()))
+    assert not failed, '\n'.join(failed)
+
+
+def test_op_conv_seam(dev):
+    """What the 3x3 / stride 1 / pad == dilation route served correctly keeps that route, bit for
+    bit: Cin 3 at dilation 1 is conv3x3_c3_nchw_to_nhwc (Cout 16: a width only that entry takes);
+    bias None with ReLU stays on naws_conv3x3_nhwc_fwd (Cout 36: % 4, not % 32) and is max(conv, 0).
+    A weight that does not match (Cin, kernel, kernel) is ERR_SHAPE on both routes."""
+    import detectron.ops as O
+    from naws_hip import lib, ops
+    x, wt, b = _layer_inputs(2, 9, 11, 3, 16, 3, seed=21)
+    for bias in (b.to(dev), None):
+        for relu in (False, True):
+            got = O.Conv(x.to(dev), wt.to(dev), bias, kernel=3, pad=1, relu=relu)
+            old = ops.nhwc_to_nchw(ops.conv3x3_c3_nchw_to_nhwc(x.to(dev), wt.to(dev), bias, relu))
+            assert torch.equal(got, old)
+            _check_layer('O.Conv 3x3 s1 p1 cin 3', got.permute(0, 2, 3, 1), x, wt,
+                         None if bias is None else b, 1, 1, 1, relu)
+    x, wt, b = _layer_inputs(2, 9, 11, 32, 36, 3, seed=22)
+    for dil in (1, 2):
+        conv = O.Conv(x.to(dev), wt.to(dev), None, kernel=3, pad=dil, dilation=dil)
+        got = O.Conv(x.to(dev), wt.to(dev), None, kernel=3, pad=dil, dilation=dil, relu=True)
+        assert torch.equal(got, torch.clamp(conv, min=0)) and bool((got == 0).any())
+        _check_layer('O.Conv 3x3 s1 cout 36', got.permute(0, 2, 3, 1), x, wt, None, 1, dil, dil, True)
+    x = torch.zeros((1, 32, 9, 11), device=dev)
+    for kw in (dict(kernel=3, pad=1), dict(kernel=3, pad=2, dilation=2),              # the old route
+               dict(kernel=3, pad=1, stride=2), dict(kernel=1, pad=0)):               # the new one
+        k = kw['kernel']
+        for shape in ((32, 64, k, k), (32, 32, k + 2, k + 2), (32, 32, k, k + 2), (32, 32, k)):
+            with pytest.raises(O.NawsError) as e:
+                O.Conv(x, torch.zeros(shape, device=dev), None, **kw)
+            assert e.value.code == lib.ERR_SHAPE, (kw, shape)
+    with pytest.raises(O.NawsError) as e:                                             # Cin 3
+        O.Conv(x[:, :3].contiguous(), torch.zeros((32, 32, 3, 3), device=dev), None, kernel=3, pad=1)
+    assert e.value.code == lib.ERR_SHAPE
+
+
 @pytest.mark.parametrize('case', [LAYERS[0], LAYERS[3], LAYERS[5]], ids=['7x7', '3x3s2', '1x1s2'])
 def test_images_do_not_mix(dev, case):
     """N = 2, image 1 all zeros but one pixel of 100 (inputs are N(0, 1)) at the top-left corner -

@@ -383,7 +383,9 @@ void gemm_f32_kernel(GemmArgs g) {
 // and every output float4 is one coalesced aux load + one coalesced store: HBM-bound.  Sums run in
 // k order like the MFMA chain.  Also reports |C| row / column maxima (NawsAmax).
 constexpr int SK_MAXK = 64;
-#ifdef NAWS_AB      // the register-resident FMA form: A/B build only (tools/bench_smallk.py)
+typedef float sk_f32x4 __attribute__((ext_vector_type(4)));
+constexpr int SKM_ROWS = 64;
+#ifdef NAWS_AB      // the two superseded forms: A/B build only (tools/bench_smallk.py)
 constexpr int SK_ROWS = 128, SK_RG = 4;
 template <int KMAX>
 __global__ __launch_bounds__(256) void gemm_smallk_nn_kernel(GemmArgs g) {
@@ -483,8 +485,6 @@ __global__ __launch_bounds__(256) void gemm_smallk_nn_kernel(GemmArgs g) {
   }
 }
 
-#endif
-
 // The same product on the fp32 MFMA (v_mfma_f32_16x16x4_f32, operands swapped so that a lane
 // holds FOUR CONSECUTIVE COLUMNS of one row: 16-byte gate loads and stores).  The register-resident
 // form above keeps K float4s of B per thread (256 VGPRs, one wave per SIMD) and spends 160 FMAs
@@ -496,10 +496,8 @@ __global__ __launch_bounds__(256) void gemm_smallk_nn_kernel(GemmArgs g) {
 // Maxima: rows through LDS (one guarded atomic per row and workgroup); columns are parked in LDS
 // too and leave at the end, four per thread in parallel - issued from the MFMA layout (16 per
 // lane, each a dependent load - compare - atomic round trip) they cost 80 us.
-typedef float sk_f32x4 __attribute__((ext_vector_type(4)));
-constexpr int SKM_ROWS = 64;
 template <int KS>
-__global__ __launch_bounds__(256) void gemm_smallk_mfma_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256) void gemm_smallk_mfma_tile_kernel(GemmArgs g) {
   constexpr int KP = KS * 4, LDA_S = KP + 1;
   constexpr bool EARLY = KS <= 10;                 // registers for the gate loads ahead of the MFMAs
   __shared__ float s_rm[SKM_ROWS][4];
@@ -656,6 +654,207 @@ __global__ __launch_bounds__(256) void gemm_smallk_mfma_kernel(GemmArgs g) {
   }
 }
 
+#endif
+
+// dZ7 = gate(dL W8) as a STREAM: with K = 2C = 40 the product is 80 flops per output element and
+// the kernel is the gate read + the store, 131 MB each on the bench shape.  The tile form it
+// replaces (A/B build, above) touched memory in the MFMA's own layout - every load / store
+// instruction 16 rows x 64 bytes, the rows a whole leading dimension apart - and reached 2.6 TB/s.
+// Here a wave-instruction covers 2 rows x 512 contiguous bytes:
+//  * a workgroup owns 64 rows x 1024 columns (as before: the maxima bookkeeping is per 1024
+//    columns) and walks them in eight stages of 128 columns; wave w owns rows 16 w .. 16 w + 15 of
+//    every stage, so a row's maxima never leave the wave;
+//  * a stage's K x 128 block of B is fetched once per workgroup with 16-byte loads, one stage
+//    ahead, and parked in LDS (row stride 144 floats: the 2 x 16-lane fragment reads of one
+//    ds_read_b32 fall on 32 distinct banks); the wave's 16 x K block of A stays in registers;
+//  * the stage's gate operand is loaded in ROW layout (lane l: row 2 i + l / 32, columns
+//    4 (l % 32) .. + 3) before the stage's MFMAs;
+//  * the accumulators (transposed 16 x 16 blocks: row = lane & 15, four consecutive columns) go
+//    through a wave-private LDS tile into the same row layout, where the gate, alpha, the
+//    optional += and the maxima are applied and the 16-byte stores leave.
+// The MFMA sequence per output element (k order, zero padding to 4 KS) is the tile form's, so
+// every bit of C is; the maxima are the same sets of values, reduced in another (free) order.
+constexpr int SKM_SC = 128;            // columns per stage
+constexpr int SKM_LDB = SKM_SC + 16;   // LDS row stride of the B stage
+constexpr int SKM_LDT = SKM_SC + 4;    // LDS row stride of the wave's transposition tile
+constexpr int skm_lds_bytes(int ks) {
+  return (ks * 4 * SKM_LDB + 4 * 16 * SKM_LDT + 1024 + SKM_ROWS) * (int)sizeof(float);
+}
+template <int KS>
+__global__ __launch_bounds__(256, 2) void gemm_smallk_mfma_kernel(GemmArgs g) {
+  constexpr int KP = KS * 4;
+  constexpr int BV = KP * (SKM_SC / 4) / 256;            // float4 of a B stage per thread
+  static_assert(KP * (SKM_SC / 4) % 256 == 0, "B stage must divide over the workgroup");
+  extern __shared__ __attribute__((aligned(16))) float skm_lds[];
+  float* s_b = skm_lds;                                   // [KP][SKM_LDB]
+  float* s_t = s_b + KP * SKM_LDB;                        // [4 waves][16][SKM_LDT]
+  float* s_cm = s_t + 4 * 16 * SKM_LDT;                   // [1024]
+  float* s_rm = s_cm + 1024;                              // [SKM_ROWS]
+  const long long bz = blockIdx.z;
+  const float* A = g.A + bz * g.sA;
+  const float* B = g.B + bz * g.sB;
+  float* C = g.C + bz * g.sC;
+  const float* aux = g.aux ? g.aux + bz * g.sC : nullptr;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l15 = lane & 15, kg = lane >> 4;
+  const int half = lane >> 5, c4 = (lane & 31) * 4;       // row layout: row 2 i + half, columns c4 .. + 3
+  const int m0 = blockIdx.y * SKM_ROWS + wave * 16;       // the wave's first row
+  const int nb0 = blockIdx.x * 1024;
+  const bool gate = g.epilogue == NAWS_EPI_GATE_POS;
+  float* tw = s_t + wave * 16 * SKM_LDT;
+
+  auto load_b = [&](int s, float4 (&r)[BV]) {             // stage s of B: global -> registers
+#pragma unroll
+    for (int v = 0; v < BV; ++v) {
+      const int f = threadIdx.x + v * 256, k = f / (SKM_SC / 4), col = nb0 + s * SKM_SC + (f % (SKM_SC / 4)) * 4;
+      r[v] = (k < g.K && col < g.N) ? *reinterpret_cast<const float4*>(B + (long long)k * g.ldb + col)
+                                    : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  auto park_b = [&](const float4 (&r)[BV]) {              // registers -> LDS
+#pragma unroll
+    for (int v = 0; v < BV; ++v) {
+      const int f = threadIdx.x + v * 256;
+      *reinterpret_cast<float4*>(s_b + (f / (SKM_SC / 4)) * SKM_LDB + (f % (SKM_SC / 4)) * 4) = r[v];
+    }
+  };
+  auto load_gate = [&](int s, sk_f32x4 (&x)[8]) {         // stage s of the gate operand, row layout
+    const int col = nb0 + s * SKM_SC + c4;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int row = m0 + 2 * i + half;
+      x[i] = sk_f32x4{1.f, 1.f, 1.f, 1.f};
+      if (gate && row < g.M && col < g.N)
+        x[i] = *reinterpret_cast<const sk_f32x4*>(aux + (long long)row * g.ldaux + col);
+    }
+  };
+
+  float4 breg[BV];
+  load_b(0, breg);
+  float a[KS];                                            // a[ks] = A[m0 + l15][ks * 4 + kg]
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int k = ks * 4 + kg;
+    a[ks] = (m0 + l15 < g.M && k < g.K) ? A[(long long)(m0 + l15) * g.lda + k] : 0.f;
+  }
+  float cmul[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int row = m0 + 2 * i + half;
+    cmul[i] = (g.am.colmul && row < g.M) ? fabsf(g.am.colmul[row]) : 1.f;
+  }
+  float rmx[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) rmx[i] = 0.f;
+  for (int i = threadIdx.x; i < 1024; i += 256) s_cm[i] = 0.f;
+  park_b(breg);
+  __syncthreads();
+
+#pragma unroll 1
+  for (int s = 0; s < 1024 / SKM_SC; ++s) {
+    const int n0 = nb0 + s * SKM_SC;
+    const bool more = s + 1 < 1024 / SKM_SC && n0 + SKM_SC < g.N;      // (workgroup-uniform)
+    sk_f32x4 xc[8];
+    load_gate(s, xc);                                     // in flight under the MFMAs
+    if (more) load_b(s + 1, breg);
+    sk_f32x4 acc[SKM_SC / 16];
+#pragma unroll
+    for (int j = 0; j < SKM_SC / 16; ++j) {
+      float b[KS];                                        // b[ks] = B[ks * 4 + kg][n0 + j * 16 + l15]
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) b[ks] = s_b[(ks * 4 + kg) * SKM_LDB + j * 16 + l15];
+      acc[j] = sk_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[ks], a[ks], acc[j], 0, 0, 0);
+    }
+    // transposed blocks -> row layout through the wave's own LDS tile (LDS serves a wave's
+    // accesses in order; the fences keep the compiler from moving them across each other)
+#pragma unroll
+    for (int j = 0; j < SKM_SC / 16; ++j)
+      *reinterpret_cast<sk_f32x4*>(tw + l15 * SKM_LDT + j * 16 + kg * 4) = acc[j];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int col = n0 + c4;
+    float cm[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int row = m0 + 2 * i + half;
+      sk_f32x4 v = *reinterpret_cast<const sk_f32x4*>(tw + (2 * i + half) * SKM_LDT + c4);
+      if (row >= g.M || col >= g.N) continue;             // N % 4 == 0: a float4 is all in or all out
+      if (gate) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = xc[i][e] > 0.f ? v[e] * g.alpha : 0.f;
+      }
+      sk_f32x4* dst = reinterpret_cast<sk_f32x4*>(C + (long long)row * g.ldc + col);
+      if (g.accumulate) {
+        const sk_f32x4 o = *dst;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] += o[e];
+      }
+      *dst = v;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float av = fabsf(v[e]);
+        rmx[i] = fmaxf(rmx[i], av);
+        cm[e] = fmaxf(cm[e], av * cmul[i]);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (g.am.colmax) {
+      // the two lane halves hold the same columns; the four waves meet in LDS (values >= 0:
+      // their bit patterns order like the floats)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float v = fmaxf(cm[e], __shfl_xor(cm[e], 32));
+        if (half == 0 && v > 0.f)
+          atomicMax(reinterpret_cast<unsigned*>(s_cm) + s * SKM_SC + c4 + e, __float_as_uint(v));
+      }
+    }
+    if (!more) break;
+    __syncthreads();                                      // every wave has its fragments of stage s
+    park_b(breg);
+    __syncthreads();
+  }
+
+  if (g.am.rowmax) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float v = rmx[i];
+#pragma unroll
+      for (int d = 16; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d));
+      if ((lane & 31) == 0) s_rm[wave * 16 + 2 * i + half] = v;
+    }
+  }
+  if (g.am.rowmax || g.am.colmax) __syncthreads();
+  const int r0 = blockIdx.y * SKM_ROWS;
+  if (g.am.rowmax && threadIdx.x < SKM_ROWS && r0 + threadIdx.x < g.M) {
+    const float m = s_rm[threadIdx.x];
+    unsigned* rowmax = g.am.rowmax + bz * g.am.sRow + (long long)(nb0 / g.am.seg_cols) * g.M;
+    if (m > 0.f) naws_atomic_max_bits(rowmax + r0 + threadIdx.x, m);
+  }
+  if (g.am.colmax) {
+    // thread t: columns t, t + 256, ... of the workgroup's 1024 - the four current maxima are
+    // fetched together (independent loads), then compared
+    unsigned* cmx = g.am.colmax + bz * g.am.sCol + nb0;
+    unsigned cur[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int col = q * 256 + threadIdx.x;
+      cur[q] = (nb0 + col < g.N)
+                   ? __hip_atomic_load(cmx + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int col = q * 256 + threadIdx.x;
+      const unsigned v = __float_as_uint(s_cm[col]);
+      if (v > cur[q] && s_cm[col] > 0.f) atomicMax(cmx + col, v);
+    }
+  }
+}
+
 // Tuning knob for A/B experiments (tools/kernel_bench.py): naws_set_variant("gemm", v)
 //   0 default, 2: pad LDS so only 1 workgroup fits a CU, 4: BK=32 tile forms
 int gemm_variant() { return naws_knob(NAWS_KNOB_GEMM); }
@@ -796,12 +995,19 @@ extern "C" int naws_gemm_f32_amax(int transA, int transB, int M, int N, int K, c
           hipLaunchKernelGGL(gemm_smallk_nn_kernel<40>, grid, dim3(256), 0, s, g);
         else
           hipLaunchKernelGGL(gemm_smallk_nn_kernel<64>, grid, dim3(256), 0, s, g);
+      } else if (gemm_variant() == 9) {
+        if (K <= 40)
+          hipLaunchKernelGGL(gemm_smallk_mfma_tile_kernel<10>, grid, dim3(256), 0, s, g);
+        else
+          hipLaunchKernelGGL(gemm_smallk_mfma_tile_kernel<16>, grid, dim3(256), 0, s, g);
       } else
 #endif
       if (K <= 40) {
-        hipLaunchKernelGGL(gemm_smallk_mfma_kernel<10>, grid, dim3(256), 0, s, g);
+        if (naws_allow_lds(gemm_smallk_mfma_kernel<10>) != NAWS_OK) return NAWS_ERR_LAUNCH;
+        hipLaunchKernelGGL(gemm_smallk_mfma_kernel<10>, grid, dim3(256), skm_lds_bytes(10), s, g);
       } else {
-        hipLaunchKernelGGL(gemm_smallk_mfma_kernel<16>, grid, dim3(256), 0, s, g);
+        if (naws_allow_lds(gemm_smallk_mfma_kernel<16>) != NAWS_OK) return NAWS_ERR_LAUNCH;
+        hipLaunchKernelGGL(gemm_smallk_mfma_kernel<16>, grid, dim3(256), skm_lds_bytes(16), s, g);
       }
       return naws_check_launch();
     }

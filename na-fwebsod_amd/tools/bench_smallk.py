@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""dZ7 = gate(dL W8) on the bench shape (M = 4000, N = 4096, K = 40, batch 2): the fp32-MFMA form
-against the register-resident FMA form it replaced (naws_set_variant('gemm', 8); only in the
-`make AB=1` library: NAWS_LIB=.../libnaws_hip_ab.so, otherwise both rows time the MFMA form), with and without the
-epilogue's |C| maxima, interleaved in one process."""
+"""dZ7 = gate(dL W8) on the bench shape (M = 4000, N = 4096, K = 40, batch 2): the streaming fp32-MFMA
+form against the two forms it replaced - the MFMA form that touched memory in the accumulator
+layout (naws_set_variant('gemm', 9)) and the register-resident FMA form (8); both only in the
+`make AB=1` library: NAWS_LIB=.../libnaws_hip_ab.so, otherwise every row times the shipped form -
+with and without the epilogue's |C| maxima, interleaved in one process."""
 import os
 import sys
 
@@ -26,7 +27,7 @@ def main():
     res = {}
     ref = None
     for rnd in range(6):
-        for var in (0, 8):
+        for var in (0, 9, 8):
             for amax in (True, False):
                 L.set_variant('gemm', var)
                 kw = {}
@@ -40,14 +41,14 @@ def main():
                 torch.cuda.synchronize()
                 if ref is None:
                     ref = out.clone()
-                assert torch.allclose(out, ref, rtol=1e-4, atol=1e-7)
+                assert torch.allclose(out, ref, rtol=1e-4, atol=1e-7), (var, amax)
                 if rnd:
                     res.setdefault((var, amax), []).append(s.elapsed_time(e))
     L.set_variant('gemm', 0)
     for (var, amax), ts in sorted(res.items()):
         ts = sorted(ts)
-        print('%-22s maxima %-5s median %.1f us (min %.1f)' % ('fp32 MFMA 16x16x4' if var == 0 else 'FMA, B in registers',
-                                                           amax, ts[len(ts) // 2] * 1e3, ts[0] * 1e3))
+        name = {0: 'fp32 MFMA, row-layout stream', 9: 'fp32 MFMA, tile layout', 8: 'FMA, B in registers'}[var]
+        print('%-28s maxima %-5s median %.1f us (min %.1f)' % (name, amax, ts[len(ts) // 2] * 1e3, ts[0] * 1e3))
     print('bytes: %.0f MB (gate read + store) -> %.0f us at 4.5 TB/s' % (2 * out.numel() * 4 / 1e6, 2 * out.numel() * 4 / 4.5e6))
 
 

@@ -1207,6 +1207,61 @@ int naws_grid_cut_fwd(const uint32_t* survive, const float* score, const int64_t
                       int64_t I, int T, const float* score_thresholds, int S, const int32_t* limits,
                       int Lc, int32_t* count, float* kth, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * f-7  Box-proposal recall (detectron/datasets/json_dataset_evaluator.py:255-336): the greedy
+ *      one-to-one matching of an image's proposals to its ground truth, for every image and every
+ *      (area range, limit) setting in ONE launch; the reference pays a dense bbox_overlaps and a
+ *      Python loop per image and setting.  One wave per (segment, setting), the grid capped at
+ *      naws_proposal_match_max_grid() workgroups of 4 waves and striding.  Does not synchronise,
+ *      allocate or use atomics; every output element has one writer.
+ *
+ * naws_proposal_match_fwd — boxes fp32 [P_total][4] (x1, y1, x2, y2; on 16 bytes), box_off int64
+ *   [S + 1]: the proposals of image s in file order; gt fp32 [G_total][4] (on 16 bytes), gt_area
+ *   fp32 [G_total] (the roidb's seg_areas), gt_off int64 [S + 1]: its ground truth with
+ *   gt_classes > 0 and is_crowd == 0, in roidb order.  area_lo / area_hi [num_areas] and limits
+ *   [num_limits] are HOST arrays (at most 64 each), copied into the launch.  Setting q = a *
+ *   num_limits + l; -> gt_iou fp32 [num_areas * num_limits][G_total].  Per segment and setting,
+ *   bit for bit what the reference's loop records:
+ *     valid gt      area_lo[a] <= gt_area <= area_hi[a], compared as fp32 (both bounds inclusive:
+ *                   an area on a bound belongs to both neighbouring ranges).  The reference's
+ *                   bounds 0, 32^2, 96^2, 128^2, 256^2, 512^2 and 1e5^2 are all exact in fp32
+ *                   (1e10 = 2^10 * 5^10, 5^10 < 2^24), so the fp32 comparison is the reference's.
+ *     prefix        P' = P when limits[l] <= 0, min(P, limits[l]) otherwise (boxes[:limit]).
+ *     rounds        for j < min(P', number of valid gt): the unused (proposal b, gt g) pair of
+ *                   greatest overlap; among equals the lowest g in roidb order, then the lowest b
+ *                   - the first maxima of overlaps.argmax(axis=0) and max_overlaps.argmax(), a
+ *                   used entry being -1 and an unused one >= 0.  The gt records that overlap.
+ *     gt_iou        a matched gt: its overlap; a valid gt never matched: 0; a gt outside the area
+ *                   range: -1 (it counts nowhere); P' == 0: every valid gt -2 (counted in num_pos,
+ *                   absent from gt_overlaps: the reference's `continue`).
+ *   The overlap is cython_bbox.pyx:27-63 as compiled: coordinate differences in fp32; `+ 1` and
+ *   the area products in double; box_area, iw, ih stored as fp32; iw > 0 && ih > 0, else 0; ua =
+ *   (double area of b + box_area - iw * ih) stored as fp32; iw * ih an fp32 product and the
+ *   quotient a correctly rounded fp32 division; nothing contracted into an FMA.  Coordinates must
+ *   be finite and the areas must not overflow (an overlap is then >= 0 and never NaN).
+ *   Each gt keeps its best unused proposal; after a round only the gt whose proposal was consumed
+ *   are computed again (about G * P overlaps per image and setting instead of G * G * P).
+ *   workspace: naws_proposal_match_workspace_bytes(max_props, max_gt) bytes on 16 bytes, max_props
+ *   / max_gt >= the longest segment of either kind.  It is the kernel's working state, nothing to
+ *   read afterwards.  (-1 from the sizer: a negative count or one above 2^31 - 1.)
+ *   Errors, all before any launch, in this order: a negative count or size -> SHAPE; num_areas or
+ *   num_limits < 1, or boxes / gt / workspace not on 16 bytes -> ARG; a null pointer that the
+ *   counts make required (the host arrays, the offsets, the workspace always) -> NULL; more than
+ *   64 areas or limits, a count above 2^31 - 1 -> UNSUPPORTED; a NaN area bound -> ARG; a
+ *   workspace smaller than the sizer says -> SHAPE.  The offset vectors live on the device: the
+ *   kernel checks them (0 <= off[s] <= off[s + 1] <= total, segment lengths within max_props /
+ *   max_gt) and a segment that fails touches nothing - its gt_iou entries keep what the caller put
+ *   there.
+ * ------------------------------------------------------------------------ */
+int naws_proposal_match_max_grid(void);
+int64_t naws_proposal_match_workspace_bytes(int64_t max_props, int64_t max_gt);
+int naws_proposal_match_fwd(const float* boxes, const int64_t* box_off, int64_t P_total,
+                            const float* gt, const float* gt_area, const int64_t* gt_off,
+                            int64_t G_total, int64_t S, const float* area_lo, const float* area_hi,
+                            int num_areas, const int32_t* limits, int num_limits, int64_t max_props,
+                            int64_t max_gt, void* workspace, int64_t workspace_bytes, float* gt_iou,
+                            void* stream);
+
 /* ---- process-wide state and tuning (no reference counterpart) ------------------------------ */
 /* Kernels that need more than 64 KB of dynamic LDS have that limit raised once per (kernel,
  * device) pair; the library remembers which pairs are done.  After hipDeviceReset() - which

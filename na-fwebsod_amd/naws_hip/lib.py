@@ -91,6 +91,7 @@ PROTOTYPES = {
     'naws_voc_ap_fwd': [p, p, p, p, i64, i32, p, p, p, p, p],
     'naws_nms_multi_fwd': [p, p, i64, i64, p, i32, p, p, p],
     'naws_grid_cut_fwd': [p, p, p, i64, i64, i32, p, i32, p, i32, p, p, p, p],
+    'naws_proposal_match_fwd': [p, p, i64, p, p, p, i64, i64, p, p, i32, p, i32, i64, i64, p, i64, p, p],
     'naws_unary_f32': [i32, p, i64, f32, f32, p, p],
     'naws_binary_f32': [i32, p, i32, i32, p, i32, i32, p, i32, i32, p],
     'naws_softmax_rows_fwd': [p, i32, i32, p, p],
@@ -168,6 +169,8 @@ SPECIAL = {
     'naws_conv2d_packed_k': ([i32, i32], i64),
     'naws_conv2d_max_grid_m': ([], i32),
     'naws_nms_workspace_bytes': ([i32, i32], i64),
+    'naws_proposal_match_max_grid': ([], i32),
+    'naws_proposal_match_workspace_bytes': ([i64, i64], i64),
     'naws_roi_label_workspace_bytes': ([i32, i32, i32], i64),
     'naws_softmax_with_loss_n_workspace_floats': ([i32], i64),
     'naws_center_loss_workspace_bytes': ([i32, i32, i32], i64),

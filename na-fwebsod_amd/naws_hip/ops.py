@@ -1877,6 +1877,66 @@ def grid_cut(survive, score, img_off, num_nms, score_thresholds, limits):
     return count, kth, status
 
 
+def proposal_match_max_grid():
+    """The most workgroups (of 4 waves) naws_proposal_match_fwd launches."""
+    return int(L.load().naws_proposal_match_max_grid())
+
+
+def proposal_match(boxes, box_off, gt, gt_area, gt_off, area_lo, area_hi, limits, out=None):
+    """boxes fp32 [P,4] and box_off int64 [S+1]: every image's proposals in file order; gt fp32
+    [G,4], gt_area fp32 [G], gt_off int64 [S+1]: its non-crowd ground truth in roidb order;
+    area_lo / area_hi / limits host values (limit <= 0: none) -> gt_iou fp32 [areas * limits, G]:
+    the matched overlap, 0 = valid and never matched, -1 = outside the area range, -2 = valid but
+    the image has no proposals; see naws_proposal_match_fwd.  The offsets are read back once: they
+    must be non-decreasing from 0 to the row count (NawsError SHAPE otherwise)."""
+    fn = 'naws_proposal_match_fwd'
+    named = [(boxes, 'boxes', _f32), (gt, 'gt', _f32), (gt_area, 'gt_area', _f32),
+             (box_off, 'box_off', torch.int64), (gt_off, 'gt_off', torch.int64)]
+    if out is not None:
+        named.append((out, 'out', _f32))
+    # dtype, layout and offsets first, residence last: a strided view or a bad offset vector is
+    # refused as such wherever its tensors live
+    for t, name, dtype in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise TypeError('%s must be a %s tensor' % (name, dtype))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+    if boxes.dim() != 2 or gt.dim() != 2 or box_off.dim() != 1 or gt_off.dim() != 1:
+        raise L.NawsError(fn, L.ERR_SHAPE)
+    np_, ng, s = boxes.shape[0], gt.shape[0], box_off.numel() - 1
+    if boxes.shape[1] != 4 or gt.shape[1] != 4 or gt_area.numel() != ng or s < 0 \
+            or gt_off.numel() != s + 1:
+        raise L.NawsError(fn, L.ERR_SHAPE)
+    lo = np.ascontiguousarray(area_lo, np.float32).reshape(-1)
+    hi = np.ascontiguousarray(area_hi, np.float32).reshape(-1)
+    lim = np.ascontiguousarray(limits, np.int32).reshape(-1)
+    if hi.size != lo.size:
+        raise L.NawsError(fn, L.ERR_SHAPE)
+    maxima = []
+    for off, total in ((box_off, np_), (gt_off, ng)):
+        o = off.cpu().numpy()
+        if o[0] != 0 or o[-1] != total or (np.diff(o) < 0).any():
+            raise L.NawsError(fn, L.ERR_SHAPE)
+        maxima.append(int(np.diff(o).max()) if s > 0 else 0)
+    nset = lo.size * lim.size
+    if out is not None and tuple(out.shape) != (nset, ng):
+        raise L.NawsError(fn, L.ERR_SHAPE)
+    for t, name, _dtype in named:
+        _chk(t, name, t.dtype)
+    dev = boxes.device
+    if out is None:
+        out = torch.empty((nset, ng), device=dev, dtype=_f32)
+    need = int(L.load().naws_proposal_match_workspace_bytes(maxima[0], maxima[1]))
+    if need < 0:
+        raise L.NawsError(fn, L.ERR_UNSUPPORTED)
+    ws = torch.empty((need,), device=dev, dtype=torch.uint8)
+    L.call(fn, boxes.data_ptr(), box_off.data_ptr(), np_, gt.data_ptr(), gt_area.data_ptr(),
+           gt_off.data_ptr(), ng, s, lo.ctypes.data if lo.size else 0, hi.ctypes.data if hi.size else 0,
+           int(lo.size), lim.ctypes.data if lim.size else 0, int(lim.size), maxima[0], maxima[1],
+           ws.data_ptr(), need, out.data_ptr(), _stream())
+    return out
+
+
 class RowmaxTable(object):
     """[(first element, end element, row length, first rowmax index)] for acm_sgd_update."""
 

@@ -3,6 +3,7 @@
 // (fp32x3 and fp16x2) and the fp16x2 halo-tile kernel with a deep weight ring.  Reference op:
 // /root/reference/detectron/modeling/VGG16.py:9-48 (Conv 3x3 pad = dilation, bias, Relu).
 #include "x3_common.h"
+#include "entry_args.h"
 
 #define g_x3_variant naws_knob(NAWS_KNOB_X3)
 
@@ -722,17 +723,11 @@ extern "C" int naws_conv3x3_nhwc_f32x3_fwd(const float* X, const void* W3, const
   if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return NAWS_ERR_SHAPE;
   if (dilation < 1) return NAWS_ERR_ARG;
   if (Cin % 16 != 0 || Cout % 4 != 0) return NAWS_ERR_UNSUPPORTED;
-  NAWS_REQUIRE_PTR(X); NAWS_REQUIRE_PTR(W3); NAWS_REQUIRE_PTR(Y);
-  if (!bias && relu) return NAWS_ERR_ARG;
-  if ((((uintptr_t)X | (uintptr_t)W3) & 15) != 0) return NAWS_ERR_ARG;
-  const long long pix = (long long)N * H * W;
-  if (pix > 0x7fffffffLL || pix * Cin * 4 > 0xFFFFFF00LL) return NAWS_ERR_UNSUPPORTED;
+  NAWS_TRY(naws_chk_conv_ptrs(X, W3, bias, relu, Y));
+  NAWS_TRY(naws_chk_conv_extent(X, W3, N, H, W, Cin));
+  const long long pix = (long long)N * H * W;          // (the tile-count rules below)
   CArgs g{};
-  g.X = X; g.B = (const unsigned short*)W3; g.bias = bias; g.Y = Y;
-  g.M = (int)pix; g.Cout = Cout; g.Cin = Cin; g.H = H; g.W = W; g.dil = dilation; g.relu = relu;
-  g.slabB = (long long)Cout * 16;
-  g.planeB = (long long)9 * Cin * Cout;
-  g.bytesX = (unsigned)(pix * Cin * 4);
+  naws_fill_conv(g, X, W3, bias, Y, N, H, W, Cin, Cout, dilation, relu);
   hipStream_t s = (hipStream_t)stream;
   // wide shallow layers (conv1_2 .. conv2_2): the halo-tile kernel with wave-private weight
   // fragments, three bf16 planes (round 4; knob "x3" = 8: the LDS-DMA halo kernel of rounds 1-3)
@@ -1468,17 +1463,10 @@ extern "C" int naws_conv3x3_nhwc_f32x3_pool_fwd(const float* X, const void* W3, 
                                                 float* Y, void* stream) {
   if (N <= 0 || H < 2 || W < 2 || Cin <= 0 || Cout <= 0) return NAWS_ERR_SHAPE;
   if (Cin % 16 != 0 || Cout % 64 != 0 || Cout > 256) return NAWS_ERR_UNSUPPORTED;
-  NAWS_REQUIRE_PTR(X); NAWS_REQUIRE_PTR(W3); NAWS_REQUIRE_PTR(Y);
-  if (!bias && relu) return NAWS_ERR_ARG;
-  if ((((uintptr_t)X | (uintptr_t)W3) & 15) != 0) return NAWS_ERR_ARG;
-  const long long pix = (long long)N * H * W;
-  if (pix > 0x7fffffffLL || pix * Cin * 4 > 0xFFFFFF00LL) return NAWS_ERR_UNSUPPORTED;
+  NAWS_TRY(naws_chk_conv_ptrs(X, W3, bias, relu, Y));
+  NAWS_TRY(naws_chk_conv_extent(X, W3, N, H, W, Cin));
   CArgs g{};
-  g.X = X; g.B = (const unsigned short*)W3; g.bias = bias; g.Y = Y;
-  g.M = (int)pix; g.Cout = Cout; g.Cin = Cin; g.H = H; g.W = W; g.dil = 1; g.relu = relu;
-  g.slabB = (long long)Cout * 16;
-  g.planeB = (long long)9 * Cin * Cout;
-  g.bytesX = (unsigned)(pix * Cin * 4);
+  naws_fill_conv(g, X, W3, bias, Y, N, H, W, Cin, Cout, 1, relu);
   g.pool = 1;
   if (3 * g.planeB * 2 > 0x7fffffffLL) return NAWS_ERR_UNSUPPORTED;
   return launch_conv_wp_x3(g, N, (hipStream_t)stream);
@@ -1496,17 +1484,10 @@ extern "C" int naws_conv3x3_nhwc_bf16_wp_fwd(const float* X, const void* W1, con
   if (dilation == 2 && pool2) return NAWS_ERR_ARG;
   if (pool2 && (H < 2 || W < 2)) return NAWS_ERR_SHAPE;
   if (Cin % 16 != 0 || (9 * Cin) % 64 != 0 || Cout % 64 != 0) return NAWS_ERR_UNSUPPORTED;
-  NAWS_REQUIRE_PTR(X); NAWS_REQUIRE_PTR(W1); NAWS_REQUIRE_PTR(Y);
-  if (!bias && relu) return NAWS_ERR_ARG;
-  if ((((uintptr_t)X | (uintptr_t)W1) & 15) != 0) return NAWS_ERR_ARG;
-  const long long pix = (long long)N * H * W;
-  if (pix > 0x7fffffffLL || pix * Cin * 4 > 0xFFFFFF00LL) return NAWS_ERR_UNSUPPORTED;
+  NAWS_TRY(naws_chk_conv_ptrs(X, W1, bias, relu, Y));
+  NAWS_TRY(naws_chk_conv_extent(X, W1, N, H, W, Cin));
   CArgs g{};
-  g.X = X; g.B = (const unsigned short*)W1; g.bias = bias; g.Y = Y;
-  g.M = (int)pix; g.Cout = Cout; g.Cin = Cin; g.H = H; g.W = W; g.dil = dilation; g.relu = relu;
-  g.slabB = (long long)Cout * 16;
-  g.planeB = (long long)9 * Cin * Cout;
-  g.bytesX = (unsigned)(pix * Cin * 4);
+  naws_fill_conv(g, X, W1, bias, Y, N, H, W, Cin, Cout, dilation, relu);
   g.pool = pool2 ? 1 : 0;
   if (g.planeB * 2 > 0x7fffffffLL) return NAWS_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
@@ -1531,19 +1512,12 @@ extern "C" int naws_conv3x3_nhwc_f16x2_fwd(const float* X, const void* W2, const
   if (dilation == 2 && pool2) return NAWS_ERR_ARG;
   if (Cin % 16 != 0 || (9 * Cin) % 32 != 0 || Cout % 32 != 0 || (Cout > 128 && Cout % 128 != 0))
     return NAWS_ERR_UNSUPPORTED;
-  NAWS_REQUIRE_PTR(X); NAWS_REQUIRE_PTR(W2); NAWS_REQUIRE_PTR(scaleW); NAWS_REQUIRE_PTR(Y);
-  NAWS_REQUIRE_PTR(amax_in);
-  if (!bias && relu) return NAWS_ERR_ARG;
+  NAWS_REQUIRE_PTR(scaleW); NAWS_REQUIRE_PTR(amax_in);
+  NAWS_TRY(naws_chk_conv_ptrs(X, W2, bias, relu, Y));
   if (!(in_mul > 0.f) || !(in_add >= 0.f) || amax_in == amax_out) return NAWS_ERR_ARG;
-  if ((((uintptr_t)X | (uintptr_t)W2) & 15) != 0) return NAWS_ERR_ARG;
-  const long long pix = (long long)N * H * W;
-  if (pix > 0x7fffffffLL || pix * Cin * 4 > 0xFFFFFF00LL) return NAWS_ERR_UNSUPPORTED;
+  NAWS_TRY(naws_chk_conv_extent(X, W2, N, H, W, Cin));
   CArgs g{};
-  g.X = X; g.B = (const unsigned short*)W2; g.bias = bias; g.Y = Y;
-  g.M = (int)pix; g.Cout = Cout; g.Cin = Cin; g.H = H; g.W = W; g.dil = dilation; g.relu = relu;
-  g.slabB = (long long)Cout * 16;
-  g.planeB = (long long)9 * Cin * Cout;
-  g.bytesX = (unsigned)(pix * Cin * 4);
+  naws_fill_conv(g, X, W2, bias, Y, N, H, W, Cin, Cout, dilation, relu);
   g.scaleB = scaleW; g.amax_in = (const unsigned*)amax_in; g.in_mul = in_mul; g.in_add = in_add;
   g.amax_out = (unsigned*)amax_out;
   g.pool = pool2 ? 1 : 0;

@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "naws_common.h"
+#include "entry_args.h"
 
 namespace {
 
@@ -347,25 +348,20 @@ extern "C" int naws_gemm_bf16_nt(int M, int N, int K, const void* A, int a_is_bf
                                  void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return NAWS_ERR_SHAPE;
   NAWS_REQUIRE_PTR(A); NAWS_REQUIRE_PTR(B); NAWS_REQUIRE_PTR(C);
-  if (epilogue < NAWS_EPI_NONE || epilogue > NAWS_EPI_GATE_POS) return NAWS_ERR_ARG;
-  if (epilogue == NAWS_EPI_GATE_POS && aux == nullptr) return NAWS_ERR_NULL;
-  if (epilogue == NAWS_EPI_BIAS_RELU_DROP && !(drop_ratio >= 0.f && drop_ratio < 1.f)) return NAWS_ERR_ARG;
+  NAWS_TRY(naws_chk_epilogue(epilogue, aux, drop_ratio));
   if (lda < K || ldb < K || ldc < N) return NAWS_ERR_SHAPE;
   // 8 consecutive k per 16/32-byte unit
   if (!al(K, 8) || !al(lda, 8) || !al(ldb, 8) || !al(strideA, 8) || !al(strideB, 8)) return NAWS_ERR_ARG;
-  if ((((uintptr_t)A | (uintptr_t)B) & 15) != 0) return NAWS_ERR_ARG;
+  if (!naws_ptrs16(A, B)) return NAWS_ERR_ARG;
   if (batch > 65535) return NAWS_ERR_UNSUPPORTED;
   const long long exA = ((long long)(M - 1) * lda + K) * (a_is_bf16 ? 2 : 4);
   const long long exB = ((long long)(N - 1) * ldb + K) * (b_is_bf16 ? 2 : 4);
   if (exA > 0xFFFFFF00LL || exB > 0xFFFFFF00LL) return NAWS_ERR_UNSUPPORTED;
   BArgs g{};
   g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sBias = strideBias;
   g.bytesA = (unsigned)exA; g.bytesB = (unsigned)exB;
-  g.bias = bias; g.aux = aux; g.ldaux = ldaux; g.alpha = alpha;
-  g.drop_thr = naws_drop_threshold(drop_ratio);
-  g.drop_scale = (float)(1.0 / (1.0 - (double)drop_ratio));
-  g.seed = seed; g.epilogue = epilogue; g.accumulate = accumulate;
+  naws_fill_epilogue(g, epilogue, bias, strideBias, aux, ldaux, alpha, drop_ratio, seed, accumulate,
+                     strideA, strideB, strideC);
   hipStream_t s = (hipStream_t)stream;
   if (a_is_bf16 && b_is_bf16) return dispatch<true, true, false>(g, batch, s);
   if (a_is_bf16) return dispatch<true, false, false>(g, batch, s);

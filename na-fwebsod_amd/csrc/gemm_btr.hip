@@ -21,6 +21,7 @@
 // replaces: FCGradient's dW for fc6 (reference detectron/modeling/wsl_heads.py:674-679 via
 // Caffe2 FCGradient), with naws_f16_planes_transpose no longer on the path.
 #include "x3_common.h"
+#include "entry_args.h"
 
 namespace {
 
@@ -111,6 +112,16 @@ bool btr_two_phase() {
   return v == 18 || v == 19;
 }
 
+// the operand fields both entry points share (ld = ldc, or ldp in the SGD form)
+void fill_btr(BArgs& g, int M, int N, int K, const void* A2, int64_t slabA, int64_t planeA,
+              const float* scaleA, const void* X2, int64_t slabX, int64_t planeX, int xrows,
+              const float* scaleX, float* C, int ld) {
+  g.A = (const unsigned short*)A2; g.X = (const unsigned short*)X2; g.C = C;
+  g.M = M; g.N = N; g.K = K; g.ldc = ld; g.xrows = xrows;
+  g.planeA = planeA; g.slabA = slabA; g.planeX = planeX; g.slabX = slabX;
+  g.rs = scaleA; g.cs = scaleX;
+}
+
 }  // namespace
 
 // C [M x N] (ld ldc) = A^T-planes x X-planes: A2 = planes [2][K/16][M][16] with per-row factors
@@ -121,17 +132,12 @@ extern "C" int naws_gemm_f32_f16x2_nt_xk(int M, int N, int K, const void* A2, in
                                          int64_t planeA, const float* scaleA, const void* X2,
                                          int64_t slabX, int64_t planeX, int xrows,
                                          const float* scaleX, float* C, int ldc, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || xrows <= 0 || xrows > K) return NAWS_ERR_SHAPE;
-  if (K % 32 != 0 || N % 16 != 0 || ldc < N || ldc % 4 != 0) return NAWS_ERR_UNSUPPORTED;
+  NAWS_TRY(naws_chk_xk_shape(M, N, K, xrows, ldc));
   NAWS_REQUIRE_PTR(A2); NAWS_REQUIRE_PTR(X2); NAWS_REQUIRE_PTR(scaleA); NAWS_REQUIRE_PTR(C);
-  if ((((uintptr_t)A2 | (uintptr_t)X2 | (uintptr_t)C) & 15) != 0) return NAWS_ERR_ARG;
-  if (scaleX && ((uintptr_t)scaleX & 15) != 0) return NAWS_ERR_ARG;
-  if (slabA < (int64_t)M * 16 || slabX < (int64_t)xrows * 16) return NAWS_ERR_ARG;
+  if (!naws_ptrs16(C)) return NAWS_ERR_ARG;
+  NAWS_TRY(naws_chk_planes_xk(M, xrows, A2, slabA, X2, slabX, scaleX));
   BArgs g{};
-  g.A = (const unsigned short*)A2; g.X = (const unsigned short*)X2; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.ldc = ldc; g.xrows = xrows;
-  g.planeA = planeA; g.slabA = slabA; g.planeX = planeX; g.slabX = slabX;
-  g.rs = scaleA; g.cs = scaleX;
+  fill_btr(g, M, N, K, A2, slabA, planeA, scaleA, X2, slabX, planeX, xrows, scaleX, C, ldc);
   hipStream_t s = (hipStream_t)stream;
   // few tiles (the column remainder of fc6's dW): 128 x 128 tiles, two workgroups per CU
   if (naws_cdiv(M, 256) * naws_cdiv(N, 256) < 256) return launch_btr<128, 128, 2, 2>(g, s);
@@ -156,25 +162,18 @@ extern "C" int naws_gemm_f32_f16x2_nt_xk_sgd(
     int nesterov, int gpu_num, int64_t iter_count, void* planes, int64_t plane_stride,
     int plane_rows, const uint32_t* bound, uint32_t* rowmax, float* inv_scale, int32_t* overflow,
     int32_t overflow_tag, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0 || xrows <= 0 || xrows > K || gpu_num <= 0 || iter_count < 0 ||
-      plane_rows <= 0)
-    return NAWS_ERR_SHAPE;
-  if (K % 32 != 0 || N % 16 != 0 || ldp < N || ldp % 4 != 0) return NAWS_ERR_UNSUPPORTED;
+  if (gpu_num <= 0 || iter_count < 0 || plane_rows <= 0) return NAWS_ERR_SHAPE;
+  NAWS_TRY(naws_chk_xk_shape(M, N, K, xrows, ldp));
   NAWS_REQUIRE_PTR(A2); NAWS_REQUIRE_PTR(X2); NAWS_REQUIRE_PTR(scaleA); NAWS_REQUIRE_PTR(param);
   NAWS_REQUIRE_PTR(momentum_buf); NAWS_REQUIRE_PTR(lr); NAWS_REQUIRE_PTR(planes);
   NAWS_REQUIRE_PTR(bound); NAWS_REQUIRE_PTR(rowmax); NAWS_REQUIRE_PTR(inv_scale);
   NAWS_REQUIRE_PTR(overflow);
-  if ((((uintptr_t)A2 | (uintptr_t)X2 | (uintptr_t)param | (uintptr_t)momentum_buf) & 15) != 0)
-    return NAWS_ERR_ARG;
+  if (!naws_ptrs16(param, momentum_buf)) return NAWS_ERR_ARG;
   if (((uintptr_t)planes & 7) != 0 || (const void*)bound == (const void*)rowmax) return NAWS_ERR_ARG;
-  if (scaleX && ((uintptr_t)scaleX & 15) != 0) return NAWS_ERR_ARG;
-  if (slabA < (int64_t)M * 16 || slabX < (int64_t)xrows * 16) return NAWS_ERR_ARG;
+  NAWS_TRY(naws_chk_planes_xk(M, xrows, A2, slabA, X2, slabX, scaleX));
   if (plane_rows < M) return NAWS_ERR_ARG;      // the block lies inside one batch item of the planes
   BArgs g{};
-  g.A = (const unsigned short*)A2; g.X = (const unsigned short*)X2; g.C = nullptr;
-  g.M = M; g.N = N; g.K = K; g.ldc = ldp; g.xrows = xrows;
-  g.planeA = planeA; g.slabA = slabA; g.planeX = planeX; g.slabX = slabX;
-  g.rs = scaleA; g.cs = scaleX;
+  fill_btr(g, M, N, K, A2, slabA, planeA, scaleA, X2, slabX, planeX, xrows, scaleX, nullptr, ldp);
   g.mom = momentum_buf; g.param = param; g.ldp = ldp; g.lr = lr; g.lr_mult = lr_mult;
   g.wd = weight_decay; g.momentum = momentum; g.gscale = (float)(1.0 / (double)gpu_num);
   g.nesterov = nesterov; g.first = iter_count == 0 ? 1 : 0;

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "naws_common.h"
+#include "entry_args.h"
 
 namespace {
 
@@ -935,6 +936,24 @@ long long extent_bytes(long long rows, long long cols, long long ld) {
 }
 constexpr long long MAX_EXTENT = 0xFFFFFFF0LL - 64;  // 32-bit buffer byte offsets
 
+// The dense fp32 operands of naws_gemm_f32_amax / naws_gemm_f32_splitk: leading dimensions hold a
+// row; 16-byte vector loads along each operand's contiguous dimension; ...
+bool dense_ld_ok(int transA, int transB, int M, int N, int K, int lda, int ldb, int ldc) {
+  return lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N;
+}
+bool dense_aligned(const float* A, int lda, int64_t strideA, const float* B, int ldb, int64_t strideB) {
+  return aligned4(lda) && aligned4(ldb) && aligned4(strideA) && aligned4(strideB) && ptr16(A) && ptr16(B);
+}
+// ... and the operand fields of GemmArgs; false when a batch slice exceeds the buffer descriptors.
+bool fill_dense(GemmArgs& g, int transA, int transB, int M, int N, int K, const float* A, int lda,
+                const float* B, int ldb) {
+  const long long exA = transA ? extent_bytes(K, M, lda) : extent_bytes(M, K, lda);
+  const long long exB = transB ? extent_bytes(N, K, ldb) : extent_bytes(K, N, ldb);
+  g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb;
+  g.bytesA = (unsigned)exA; g.bytesB = (unsigned)exB;
+  return exA <= MAX_EXTENT && exB <= MAX_EXTENT;
+}
+
 }  // namespace
 
 extern "C" int naws_gemm_f32_amax(int transA, int transB, int M, int N, int K, const float* A,
@@ -946,38 +965,17 @@ extern "C" int naws_gemm_f32_amax(int transA, int transB, int M, int N, int K, c
                                   uint32_t* colmax, const float* colmax_rowmul, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return NAWS_ERR_SHAPE;
   NAWS_REQUIRE_PTR(A); NAWS_REQUIRE_PTR(B); NAWS_REQUIRE_PTR(C);
-  if (epilogue < NAWS_EPI_NONE || epilogue > NAWS_EPI_GATE_POS) return NAWS_ERR_ARG;
-  if (epilogue == NAWS_EPI_GATE_POS && aux == nullptr) return NAWS_ERR_NULL;
-  if (epilogue == NAWS_EPI_BIAS_RELU_DROP && !(drop_ratio >= 0.f && drop_ratio < 1.f))
-    return NAWS_ERR_ARG;
-  if (lda < (transA ? M : K) || ldb < (transB ? K : N) || ldc < N) return NAWS_ERR_SHAPE;
-  // 16-byte vector loads along each operand's contiguous dimension
-  if (!aligned4(lda) || !aligned4(ldb) || !aligned4(strideA) || !aligned4(strideB) ||
-      !ptr16(A) || !ptr16(B))
-    return NAWS_ERR_ARG;
+  NAWS_TRY(naws_chk_epilogue(epilogue, aux, drop_ratio));
+  if (!dense_ld_ok(transA, transB, M, N, K, lda, ldb, ldc)) return NAWS_ERR_SHAPE;
+  if (!dense_aligned(A, lda, strideA, B, ldb, strideB)) return NAWS_ERR_ARG;
   if (!aligned4(transA ? M : K) || !aligned4(transB ? K : N)) return NAWS_ERR_ARG;
   if (batch > 65535) return NAWS_ERR_UNSUPPORTED;
-  const long long exA = transA ? extent_bytes(K, M, lda) : extent_bytes(M, K, lda);
-  const long long exB = transB ? extent_bytes(N, K, ldb) : extent_bytes(K, N, ldb);
-  if (exA > MAX_EXTENT || exB > MAX_EXTENT) return NAWS_ERR_UNSUPPORTED;
-
   GemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sBias = strideBias;
-  g.bytesA = (unsigned)exA; g.bytesB = (unsigned)exB;
-  g.bias = bias; g.aux = aux; g.ldaux = ldaux; g.alpha = alpha;
-  g.drop_thr = naws_drop_threshold(drop_ratio);
-  g.drop_scale = (float)(1.0 / (1.0 - (double)drop_ratio));
-  g.seed = seed; g.epilogue = epilogue; g.accumulate = accumulate;
-  if (rowmax || colmax) {
-    const int seg = rowmax_seg_cols > 0 ? rowmax_seg_cols : N;
-    if (rowmax && seg < N && seg % 256 != 0) return NAWS_ERR_ARG;
-    const int nseg = (int)naws_cdiv(N, seg);
-    g.am.rowmax = rowmax; g.am.colmax = colmax; g.am.colmul = colmax_rowmul;
-    g.am.seg_cols = seg >= N ? 0x40000000 : seg;
-    g.am.sRow = (long long)nseg * M; g.am.sCol = N;
-  }
+  if (!fill_dense(g, transA, transB, M, N, K, A, lda, B, ldb)) return NAWS_ERR_UNSUPPORTED;
+  g.C = C; g.ldc = ldc;
+  naws_fill_epilogue(g, epilogue, bias, strideBias, aux, ldaux, alpha, drop_ratio, seed, accumulate,
+                     strideA, strideB, strideC);
+  NAWS_TRY(naws_fill_amax(g.am, M, N, rowmax, rowmax_seg_cols, colmax, colmax_rowmul));
   hipStream_t s = (hipStream_t)stream;
   // short inner dimension, plain NN form (dZ7 = gate(dL W8), K = 2C): the register-resident kernel
   if (!transA && !transB && K <= SK_MAXK && N % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C & 15) == 0 &&
@@ -1039,22 +1037,18 @@ extern "C" int naws_gemm_f32_splitk(int transA, int transB, int M, int N, int K,
   NAWS_REQUIRE_PTR(A); NAWS_REQUIRE_PTR(B); NAWS_REQUIRE_PTR(C); NAWS_REQUIRE_PTR(workspace);
   if (epilogue != NAWS_EPI_NONE && epilogue != NAWS_EPI_BIAS) return NAWS_ERR_UNSUPPORTED;
   if (epilogue == NAWS_EPI_BIAS) NAWS_REQUIRE_PTR(bias);
-  if (!aligned4(lda) || !aligned4(ldb) || !aligned4(strideA) || !aligned4(strideB) || !ptr16(A) ||
-      !ptr16(B))
-    return NAWS_ERR_ARG;
-  if (lda < (transA ? M : K) || ldb < (transB ? K : N) || ldc < N) return NAWS_ERR_ARG;
-  const long long exA = transA ? extent_bytes(K, M, lda) : extent_bytes(M, K, lda);
-  const long long exB = transB ? extent_bytes(N, K, ldb) : extent_bytes(K, N, ldb);
-  if (exA > MAX_EXTENT || exB > MAX_EXTENT || (long long)batch * ksplit > 65535) return NAWS_ERR_UNSUPPORTED;
+  // (here a short leading dimension is an argument error, not a shape error as in naws_gemm_f32_amax)
+  if (!dense_aligned(A, lda, strideA, B, ldb, strideB)) return NAWS_ERR_ARG;
+  if (!dense_ld_ok(transA, transB, M, N, K, lda, ldb, ldc)) return NAWS_ERR_ARG;
+  GemmArgs g{};
+  if (!fill_dense(g, transA, transB, M, N, K, A, lda, B, ldb) || (long long)batch * ksplit > 65535)
+    return NAWS_ERR_UNSUPPORTED;
   // every slice at least one 32-deep K-step
   const int Tall = (int)naws_cdiv(K, 32);
   int ks = std::min(ksplit, Tall);
   while (ks > 1 && (long long)(ks - 1) * naws_cdiv(Tall, ks) >= Tall) --ks;
-  GemmArgs g{};
-  g.A = A; g.B = B; g.C = workspace; g.M = M; g.N = N; g.K = K;
-  g.lda = lda; g.ldb = ldb; g.ldc = N;
+  g.C = workspace; g.ldc = N;
   g.sA = strideA; g.sB = strideB; g.sC = (long long)M * N;
-  g.bytesA = (unsigned)exA; g.bytesB = (unsigned)exB;
   g.epilogue = NAWS_EPI_NONE; g.ksplit = ks;
   hipStream_t s = (hipStream_t)stream;
   int rc;

@@ -27,6 +27,7 @@
 // replaces: Caffe2 FC / FCGradient for fc6 / fc7 (reference detectron/modeling/wsl_heads.py:
 // 674-679, webly_heads.py:490-498), same as gemm_f32.hip.
 #include "x3_common.h"
+#include "entry_args.h"
 
 #define g_x3_variant naws_knob(NAWS_KNOB_X3)
 
@@ -736,27 +737,15 @@ extern "C" int naws_gemm_f32x3_nt(int M, int N, int K, const void* A3, int64_t s
                                   float drop_ratio, uint64_t seed, int accumulate, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return NAWS_ERR_SHAPE;
   NAWS_REQUIRE_PTR(A3); NAWS_REQUIRE_PTR(B3); NAWS_REQUIRE_PTR(C);
-  if (epilogue < NAWS_EPI_NONE || epilogue > NAWS_EPI_GATE_POS) return NAWS_ERR_ARG;
-  if (epilogue == NAWS_EPI_GATE_POS && aux == nullptr) return NAWS_ERR_NULL;
-  if (epilogue == NAWS_EPI_BIAS_RELU_DROP && !(drop_ratio >= 0.f && drop_ratio < 1.f)) return NAWS_ERR_ARG;
-  if (slabA < (int64_t)M * 16 || slabB < (int64_t)N * 16 || ldc < N) return NAWS_ERR_SHAPE;
-  if (K % 16 != 0 || slabA % 8 != 0 || slabB % 8 != 0 || planeA % 8 != 0 || planeB % 8 != 0 ||
-      strideA % 8 != 0 || strideB % 8 != 0)
-    return NAWS_ERR_ARG;
-  if ((((uintptr_t)A3 | (uintptr_t)B3) & 15) != 0) return NAWS_ERR_ARG;
-  if (batch > 65535) return NAWS_ERR_UNSUPPORTED;
-  if ((long long)(M - 1) * ldc + N > 0x7fffffffLL ||
-      (aux && (long long)(M - 1) * ldaux + N > 0x7fffffffLL))
-    return NAWS_ERR_UNSUPPORTED;
+  NAWS_TRY(naws_chk_epilogue(epilogue, aux, drop_ratio));
+  NAWS_TRY(naws_chk_planes_nt(M, N, K, 16, A3, slabA, planeA, strideA, B3, slabB, planeB, strideB, ldc));
+  NAWS_TRY(naws_chk_batch_extent(batch, M, N, ldc, aux, ldaux));
   XArgs g{};
   g.A = (const unsigned short*)A3; g.B = (const unsigned short*)B3; g.C = C;
   g.M = M; g.N = N; g.K = K; g.ldc = ldc;
   g.planeA = planeA; g.planeB = planeB; g.slabA = slabA; g.slabB = slabB;
-  g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sBias = strideBias;
-  g.bias = bias; g.aux = aux; g.ldaux = ldaux; g.alpha = alpha;
-  g.drop_thr = naws_drop_threshold(drop_ratio);
-  g.drop_scale = (float)(1.0 / (1.0 - (double)drop_ratio));
-  g.seed = seed; g.epilogue = epilogue; g.accumulate = accumulate;
+  naws_fill_epilogue(g, epilogue, bias, strideBias, aux, ldaux, alpha, drop_ratio, seed, accumulate,
+                     strideA, strideB, strideC);
   hipStream_t s = (hipStream_t)stream;
   if (N <= 64 || M <= 128) return launch_x3<128, 128, 2, 2, 2>(g, batch, s);
   // short K (the Winograd batch GEMMs): prologue and epilogue are a large share of a tile's life,
@@ -932,38 +921,18 @@ static int gemm_f32_f16x2_nt_impl(int M, int N, int K, const void* A2, int64_t s
   if (drop_ld > 0 && batch != 1) return NAWS_ERR_UNSUPPORTED;
   NAWS_REQUIRE_PTR(A2); NAWS_REQUIRE_PTR(B2); NAWS_REQUIRE_PTR(C);
   NAWS_REQUIRE_PTR(scaleA); NAWS_REQUIRE_PTR(scaleB);
-  if (epilogue < NAWS_EPI_NONE || epilogue > NAWS_EPI_GATE_POS) return NAWS_ERR_ARG;
-  if (epilogue == NAWS_EPI_GATE_POS && aux == nullptr) return NAWS_ERR_NULL;
-  if (epilogue == NAWS_EPI_BIAS_RELU_DROP && !(drop_ratio >= 0.f && drop_ratio < 1.f)) return NAWS_ERR_ARG;
-  if (slabA < (int64_t)M * 16 || slabB < (int64_t)N * 16 || ldc < N) return NAWS_ERR_SHAPE;
-  if (K % 32 != 0 || slabA % 8 != 0 || slabB % 8 != 0 || planeA % 8 != 0 || planeB % 8 != 0 ||
-      strideA % 8 != 0 || strideB % 8 != 0)
-    return NAWS_ERR_ARG;
-  if ((((uintptr_t)A2 | (uintptr_t)B2) & 15) != 0) return NAWS_ERR_ARG;
-  if (batch > 65535) return NAWS_ERR_UNSUPPORTED;
-  if ((long long)(M - 1) * ldc + N > 0x7fffffffLL ||
-      (aux && (long long)(M - 1) * ldaux + N > 0x7fffffffLL))
-    return NAWS_ERR_UNSUPPORTED;
+  NAWS_TRY(naws_chk_epilogue(epilogue, aux, drop_ratio));
+  NAWS_TRY(naws_chk_planes_nt(M, N, K, 32, A2, slabA, planeA, strideA, B2, slabB, planeB, strideB, ldc));
+  NAWS_TRY(naws_chk_batch_extent(batch, M, N, ldc, aux, ldaux));
   XArgs g{};
   g.A = (const unsigned short*)A2; g.B = (const unsigned short*)B2; g.C = C;
   g.M = M; g.N = N; g.K = K; g.ldc = ldc;
   g.planeA = planeA; g.planeB = planeB; g.slabA = slabA; g.slabB = slabB;
-  g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sBias = strideBias;
-  g.bias = bias; g.aux = aux; g.ldaux = ldaux; g.alpha = alpha;
-  g.drop_thr = naws_drop_threshold(drop_ratio);
-  g.drop_scale = (float)(1.0 / (1.0 - (double)drop_ratio));
-  g.seed = seed; g.epilogue = epilogue; g.accumulate = accumulate;
+  naws_fill_epilogue(g, epilogue, bias, strideBias, aux, ldaux, alpha, drop_ratio, seed, accumulate,
+                     strideA, strideB, strideC);
   g.drop_ld = drop_ld; g.drop_c0 = drop_col0;
   g.rs = scaleA; g.cs = scaleB; g.sRs = strideScaleA; g.sCs = strideScaleB;
-  if (rowmax || colmax) {
-    // a wave's columns must lie in one rowmax segment: segments are multiples of the widest tile
-    const int seg = rowmax_seg_cols > 0 ? rowmax_seg_cols : N;
-    if (rowmax && seg < N && seg % 256 != 0) return NAWS_ERR_ARG;
-    const int nseg = (int)naws_cdiv(N, seg);
-    g.am.rowmax = rowmax; g.am.colmax = colmax; g.am.colmul = colmax_rowmul;
-    g.am.seg_cols = seg >= N ? 0x40000000 : seg;
-    g.am.sRow = (long long)nseg * M; g.am.sCol = N;
-  }
+  NAWS_TRY(naws_fill_amax(g.am, M, N, rowmax, rowmax_seg_cols, colmax, colmax_rowmul));
   hipStream_t s = (hipStream_t)stream;
   // (a column range of a wider product takes the kernel the full-width launch would take: the
   // pieces are then bit-identical to it at every size, not only where both land on one form)
@@ -1144,11 +1113,10 @@ extern "C" int naws_gemm_bf16_slab_nt_sgd(int M, int N, int K, const void* A, in
   if (M <= 0 || N <= 0 || K <= 0 || gpu_num <= 0 || prows < M || ldp < N) return NAWS_ERR_SHAPE;
   NAWS_REQUIRE_PTR(A); NAWS_REQUIRE_PTR(B); NAWS_REQUIRE_PTR(momentum_buf); NAWS_REQUIRE_PTR(param);
   NAWS_REQUIRE_PTR(lr); NAWS_REQUIRE_PTR(P);
-  if (slabA < (int64_t)M * 16 || slabB < (int64_t)N * 16) return NAWS_ERR_SHAPE;
-  if (K % 64 != 0 || N % 16 != 0 || ldp % 4 != 0 || slabA % 8 != 0 || slabB % 8 != 0) return NAWS_ERR_ARG;
-  if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)momentum_buf | (uintptr_t)param | (uintptr_t)P) & 15) != 0)
+  // (one plane, one batch item; ldp >= N was checked with the dimensions)
+  NAWS_TRY(naws_chk_planes_nt(M, N, K, 64, A, slabA, 0, 0, B, slabB, 0, 0, ldp));
+  if (N % 16 != 0 || ldp % 4 != 0 || !naws_ptrs16(momentum_buf, param, P) || iter_count < 0)
     return NAWS_ERR_ARG;
-  if (iter_count < 0) return NAWS_ERR_ARG;
   XArgs g{};
   g.A = (const unsigned short*)A; g.B = (const unsigned short*)B; g.C = nullptr;
   g.M = M; g.N = N; g.K = K; g.ldc = ldp;
@@ -1168,26 +1136,16 @@ extern "C" int naws_gemm_bf16_slab_nt(int M, int N, int K, const void* A, int64_
                                       uint64_t seed, int accumulate, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return NAWS_ERR_SHAPE;
   NAWS_REQUIRE_PTR(A); NAWS_REQUIRE_PTR(B); NAWS_REQUIRE_PTR(C);
-  if (epilogue < NAWS_EPI_NONE || epilogue > NAWS_EPI_GATE_POS) return NAWS_ERR_ARG;
-  if (epilogue == NAWS_EPI_GATE_POS && aux == nullptr) return NAWS_ERR_NULL;
-  if (epilogue == NAWS_EPI_BIAS_RELU_DROP && !(drop_ratio >= 0.f && drop_ratio < 1.f)) return NAWS_ERR_ARG;
-  if (slabA < (int64_t)M * 16 || slabB < (int64_t)N * 16 || ldc < N) return NAWS_ERR_SHAPE;
-  if (K % 64 != 0 || slabA % 8 != 0 || slabB % 8 != 0 || strideA % 8 != 0 || strideB % 8 != 0)
-    return NAWS_ERR_ARG;
-  if ((((uintptr_t)A | (uintptr_t)B) & 15) != 0) return NAWS_ERR_ARG;
-  if (batch > 65535) return NAWS_ERR_UNSUPPORTED;
-  if ((long long)(M - 1) * ldc + N > 0x7fffffffLL ||
-      (aux && (long long)(M - 1) * ldaux + N > 0x7fffffffLL))
-    return NAWS_ERR_UNSUPPORTED;
+  NAWS_TRY(naws_chk_epilogue(epilogue, aux, drop_ratio));
+  // K % 64: the one-plane kernels walk 64-deep K-steps (naws_to_bf16_slab pads K to 64)
+  NAWS_TRY(naws_chk_planes_nt(M, N, K, 64, A, slabA, 0, strideA, B, slabB, 0, strideB, ldc));
+  NAWS_TRY(naws_chk_batch_extent(batch, M, N, ldc, aux, ldaux));
   XArgs g{};
   g.A = (const unsigned short*)A; g.B = (const unsigned short*)B; g.C = C;
   g.M = M; g.N = N; g.K = K; g.ldc = ldc;
   g.slabA = slabA; g.slabB = slabB;
-  g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sBias = strideBias;
-  g.bias = bias; g.aux = aux; g.ldaux = ldaux; g.alpha = alpha;
-  g.drop_thr = naws_drop_threshold(drop_ratio);
-  g.drop_scale = (float)(1.0 / (1.0 - (double)drop_ratio));
-  g.seed = seed; g.epilogue = epilogue; g.accumulate = accumulate;
+  naws_fill_epilogue(g, epilogue, bias, strideBias, aux, ldaux, alpha, drop_ratio, seed, accumulate,
+                     strideA, strideB, strideC);
   hipStream_t s = (hipStream_t)stream;
   if (N <= 64 || M <= 128) return launch_x3<128, 128, 2, 2, 2, 1, 4>(g, batch, s);
   if (g_h2_variant == 9) return launch_x3<256, 256, 2, 4, 2, 1, 4>(g, batch, s);

@@ -45,6 +45,80 @@ def _workspace(workspace, need, device, sizer, dtype=_f32):
     return workspace
 
 
+def _conv_out(out, shape, device, check=False):
+    """A conv wrapper's output: the caller's `out` or a fresh fp32 `shape`.  check: refuse an `out`
+    of another shape / dtype / layout (the wrappers that always did; the others trust the caller)."""
+    y = out if out is not None else torch.empty(shape, device=device, dtype=_f32)
+    if check and (tuple(y.shape) != shape or y.dtype != _f32 or not y.is_contiguous()):
+        raise TypeError('out must be a contiguous fp32 %s tensor' % (shape,))
+    return y
+
+
+def _dense_pair(fn, a, b, trans_a, trans_b, dtypes, kind):
+    """Row-major 2-D (or batched 3-D) GEMM operands, last dim contiguous ->
+    (batched, batch, m, n, k, lda, ldb, sa, sb)."""
+    batched = a.dim() == 3
+    a2, b2 = (a[0], b[0]) if batched else (a, b)
+    for t, nm in ((a2, 'A'), (b2, 'B')):
+        if not t.is_cuda or t.dtype not in dtypes or t.stride(-1) != 1:
+            raise TypeError('%s must be a HIP %s tensor with a contiguous last dim' % (nm, kind))
+    m, k = (a2.shape[1], a2.shape[0]) if trans_a else (a2.shape[0], a2.shape[1])
+    n, kb = (b2.shape[0], b2.shape[1]) if trans_b else (b2.shape[1], b2.shape[0])
+    if k != kb:
+        raise L.NawsError(fn, L.ERR_SHAPE)
+    return (batched, a.shape[0] if batched else 1, m, n, k, a2.stride(0), b2.stride(0),
+            a.stride(0) if batched else 0, b.stride(0) if batched else 0)
+
+
+def _planes(t, dtype, nplanes, batched):
+    """One K-slab-major operand [nplanes (if any), (b,) K/16, rows, 16] ->
+    (ptr, slab stride, plane stride, batch stride, rows, K).  batched: None where the entry point
+    takes unbatched operands only, else whether the call is batched (decided by its first operand)."""
+    lead = 1 if nplanes else 0
+    if (not t.is_cuda or t.dtype != dtype or (batched is None and t.dim() != 3 + lead)
+            or (nplanes and t.shape[0] != nplanes) or t.shape[-1] != 16 or t.stride(-1) != 1
+            or t.stride(-2) != 16):
+        raise TypeError('operands must be %s%s %s%sK/16, rows, 16]' % (
+            'unbatched ' if batched is None else '', 'bf16' if dtype == torch.bfloat16 else 'f16',
+            'split planes [%d, ' % nplanes if nplanes else 'slab tensors [',
+            '' if batched is None else '..., '))
+    return (t.data_ptr(), t.stride(-3), t.stride(0) if nplanes else 0,
+            t.stride(lead) if batched else 0, t.shape[-2], t.shape[-3] * 16)
+
+
+def _gemm_out(out, batched, batch, m, n, device):
+    """-> (out, ldc, batch stride): the caller's (row-strided) `out` or a fresh one."""
+    if out is None:
+        out = torch.empty(((batch, m, n) if batched else (m, n)), device=device, dtype=_f32)
+    return out, (out[0] if batched else out).stride(0), out.stride(0) if batched else 0
+
+
+def _sbias(bias):
+    return bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
+
+
+def _epilogue_tail(fn, out, batch, epilogue, bias, aux, alpha, drop_ratio, seed, accumulate):
+    """The epilogue arguments every GEMM entry point ends with.  The kernels step a batched aux by
+    the OUTPUT's batch stride (include/naws.h: "aux stride by strideC"): a batched call takes a
+    3-D aux whose batch stride equals out's."""
+    if aux is not None and batch > 1 and (aux.dim() != 3 or aux.stride(0) != out.stride(0)):
+        raise L.NawsError(fn, L.ERR_ARG)
+    return (epilogue, _ptr(bias), _sbias(bias), _ptr(aux), (aux.stride(-2) if aux is not None else 0),
+            float(alpha), float(drop_ratio), int(seed) & 0xFFFFFFFFFFFFFFFF, int(accumulate))
+
+
+def _split_source(x, check=True):
+    """fp32 [rows, cols] or [b, rows, cols], last dim contiguous ->
+    (batched, batch, rows, cols, ld, batch stride)."""
+    batched = x.dim() == 3
+    x2 = x[0] if batched else x
+    if check and (not x.is_cuda or x.dtype != _f32 or x2.stride(1) != 1):
+        raise TypeError('x must be a HIP fp32 tensor with a contiguous last dim')
+    rows, cols = x2.shape
+    return (batched, x.shape[0] if batched else 1, rows, cols, x2.stride(0),
+            x.stride(0) if batched else 0)
+
+
 # ----------------------------------------------------------------------------
 # conv body
 # ----------------------------------------------------------------------------
@@ -53,7 +127,7 @@ def conv3x3_c3_nchw_to_nhwc(x, w_oihw, bias, relu=True, out=None):
     n, c, h, w = x.shape
     assert c == 3 and tuple(w_oihw.shape[1:]) == (3, 3, 3)
     cout = w_oihw.shape[0]
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
+    y = _conv_out(out, (n, h, w, cout), x.device)
     L.call('naws_conv3x3_c3_nchw_to_nhwc_fwd', x.data_ptr(), w_oihw.data_ptr(), _ptr(bias),
            n, h, w, cout, int(relu), y.data_ptr(), _stream())
     return y
@@ -71,7 +145,7 @@ def conv3x3_nhwc(x, w_packed, bias, dilation=1, relu=True, out=None):
     _chk(x, 'x'); _chk(w_packed, 'w_packed')
     n, h, w, cin = x.shape
     cout = w_packed.shape[0]
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
+    y = _conv_out(out, (n, h, w, cout), x.device)
     L.call('naws_conv3x3_nhwc_fwd', x.data_ptr(), w_packed.data_ptr(), _ptr(bias), n, h, w, cin,
            cout, dilation, int(relu), y.data_ptr(), _stream())
     return y
@@ -98,7 +172,7 @@ def conv3x3_winograd_nhwc(x, u, bias, dilation=1, relu=True, out=None, workspace
     _chk(x, 'x'); _chk(u, 'U')
     n, h, w, cin = x.shape
     cout = u.shape[1]
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
+    y = _conv_out(out, (n, h, w, cout), x.device)
     nws = L.load().naws_winograd_workspace_floats(n, h, w, cin, cout, dilation)
     ws = _workspace(workspace, nws, x.device, 'naws_winograd_workspace_floats')
     L.call('naws_conv3x3_winograd_nhwc_fwd', x.data_ptr(), u.data_ptr(), _ptr(bias), n, h, w, cin,
@@ -591,13 +665,6 @@ def _amax_args(rowmax, rowmax_seg, colmax, colmax_rowmul):
     return (_ptr(rowmax), int(rowmax_seg), _ptr(colmax), _ptr(colmax_rowmul))
 
 
-def _chk_batched_aux(fn, aux, out, batch):
-    """The GEMM kernels step a batched aux by the OUTPUT's batch stride (include/naws.h: "aux
-    stride by strideC"): a batched call takes a 3-D aux whose batch stride equals out's."""
-    if aux is not None and batch > 1 and (aux.dim() != 3 or aux.stride(0) != out.stride(0)):
-        raise L.NawsError(fn, L.ERR_ARG)
-
-
 def gemm(a, b, trans_a=False, trans_b=False, out=None, epilogue=L.EPI_NONE, bias=None, aux=None,
          alpha=1.0, drop_ratio=0.0, seed=0, accumulate=False, rowmax=None, rowmax_seg=0,
          colmax=None, colmax_rowmul=None):
@@ -605,36 +672,13 @@ def gemm(a, b, trans_a=False, trans_b=False, out=None, epilogue=L.EPI_NONE, bias
     row-strided views (last dim contiguous).  rowmax / colmax (zeroed int32 [batch, nseg, M] /
     [batch, N]): receive the bit patterns of max|C| per row (per column segment of rowmax_seg
     columns) / per column (of diag(colmax_rowmul) C) - what split_f16x2_dual consumes."""
-    batched = a.dim() == 3
-    if batched:
-        batch = a.shape[0]
-        a2, b2 = a[0], b[0]
-    else:
-        batch, a2, b2 = 1, a, b
-    for t, nm in ((a2, 'A'), (b2, 'B')):
-        if not t.is_cuda or t.dtype != _f32 or t.stride(-1) != 1:
-            raise TypeError('%s must be a HIP fp32 tensor with a contiguous last dim' % nm)
-    m = a2.shape[1] if trans_a else a2.shape[0]
-    k = a2.shape[0] if trans_a else a2.shape[1]
-    kb = b2.shape[1] if trans_b else b2.shape[0]
-    n = b2.shape[0] if trans_b else b2.shape[1]
-    if k != kb:
-        raise L.NawsError('naws_gemm_f32', L.ERR_SHAPE)
-    if out is None:
-        out = torch.empty(((batch, m, n) if batched else (m, n)), device=a.device, dtype=_f32)
-    c2 = out[0] if batched else out
-    sa = a.stride(0) if batched else 0
-    sb = b.stride(0) if batched else 0
-    sc = out.stride(0) if batched else 0
-    sbias = 0
-    if bias is not None and bias.dim() == 2:
-        sbias = bias.stride(0)
-    _chk_batched_aux('naws_gemm_f32_amax', aux, out, batch)
-    L.call('naws_gemm_f32_amax', int(trans_a), int(trans_b), m, n, k, a.data_ptr(), a2.stride(0),
-           b.data_ptr(), b2.stride(0), out.data_ptr(), c2.stride(0), batch, sa, sb, sc,
-           epilogue, _ptr(bias), sbias, _ptr(aux),
-           (aux.stride(-2) if aux is not None else 0), float(alpha), float(drop_ratio),
-           int(seed) & 0xFFFFFFFFFFFFFFFF, int(accumulate),
+    batched, batch, m, n, k, lda, ldb, sa, sb = _dense_pair('naws_gemm_f32', a, b, trans_a, trans_b,
+                                                            (_f32,), 'fp32')
+    out, ldc, sc = _gemm_out(out, batched, batch, m, n, a.device)
+    L.call('naws_gemm_f32_amax', int(trans_a), int(trans_b), m, n, k, a.data_ptr(), lda, b.data_ptr(),
+           ldb, out.data_ptr(), ldc, batch, sa, sb, sc,
+           *_epilogue_tail('naws_gemm_f32_amax', out, batch, epilogue, bias, aux, alpha, drop_ratio,
+                           seed, accumulate),
            *_amax_args(rowmax, rowmax_seg, colmax, colmax_rowmul), _stream())
     return out
 
@@ -644,35 +688,17 @@ def gemm_splitk(a, b, trans_a=False, trans_b=False, out=None, epilogue=L.EPI_NON
     """gemm() for a small output with a long inner dimension (fc8 forward / wgrad): K in `ksplit`
     slices, partial products in `workspace` (fp32, >= M * N * batch * ksplit floats; allocated when
     None), summed in slice order by a second pass that applies the epilogue (NONE / BIAS)."""
-    batched = a.dim() == 3
-    if batched:
-        batch = a.shape[0]
-        a2, b2 = a[0], b[0]
-    else:
-        batch, a2, b2 = 1, a, b
-    for t, nm in ((a2, 'A'), (b2, 'B')):
-        if not t.is_cuda or t.dtype != _f32 or t.stride(-1) != 1:
-            raise TypeError('%s must be a HIP fp32 tensor with a contiguous last dim' % nm)
-    m = a2.shape[1] if trans_a else a2.shape[0]
-    k = a2.shape[0] if trans_a else a2.shape[1]
-    kb = b2.shape[1] if trans_b else b2.shape[0]
-    n = b2.shape[0] if trans_b else b2.shape[1]
-    if k != kb:
-        raise L.NawsError('naws_gemm_f32_splitk', L.ERR_SHAPE)
-    if out is None:
-        out = torch.empty(((batch, m, n) if batched else (m, n)), device=a.device, dtype=_f32)
-    c2 = out[0] if batched else out
+    batched, batch, m, n, k, lda, ldb, sa, sb = _dense_pair('naws_gemm_f32_splitk', a, b, trans_a,
+                                                            trans_b, (_f32,), 'fp32')
+    out, ldc, sc = _gemm_out(out, batched, batch, m, n, a.device)
     need = m * n * batch * int(ksplit)
     if workspace is None:
         workspace = torch.empty((need,), device=a.device, dtype=_f32)
     if workspace.dtype != _f32 or workspace.numel() < need or not workspace.is_contiguous():
         raise TypeError('workspace: contiguous fp32, >= M * N * batch * ksplit floats')
-    sbias = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
-    L.call('naws_gemm_f32_splitk', int(trans_a), int(trans_b), m, n, k, a.data_ptr(), a2.stride(0),
-           b.data_ptr(), b2.stride(0), out.data_ptr(), c2.stride(0), batch,
-           (a.stride(0) if batched else 0), (b.stride(0) if batched else 0),
-           (out.stride(0) if batched else 0), epilogue, _ptr(bias), sbias, int(ksplit),
-           workspace.data_ptr(), _stream())
+    L.call('naws_gemm_f32_splitk', int(trans_a), int(trans_b), m, n, k, a.data_ptr(), lda,
+           b.data_ptr(), ldb, out.data_ptr(), ldc, batch, sa, sb, sc, epilogue, _ptr(bias),
+           _sbias(bias), int(ksplit), workspace.data_ptr(), _stream())
     return out
 
 
@@ -680,44 +706,25 @@ def gemm_bf16_nt(a, b, out=None, epilogue=L.EPI_NONE, bias=None, aux=None, alpha
                  drop_ratio=0.0, seed=0, accumulate=False):
     """C[M,N] (+)= A[M,K] B[N,K]^T with bf16 MFMA / fp32 accumulate.  a and b are 2-D (or batched
     3-D) row-strided views, each fp32 (rounded in-kernel) or bf16."""
-    batched = a.dim() == 3
-    a2, b2 = (a[0], b[0]) if batched else (a, b)
-    batch = a.shape[0] if batched else 1
-    for t, nm in ((a2, 'A'), (b2, 'B')):
-        if not t.is_cuda or t.dtype not in (_f32, torch.bfloat16) or t.stride(-1) != 1:
-            raise TypeError('%s must be a HIP fp32/bf16 tensor with a contiguous last dim' % nm)
-    m, k = a2.shape
-    n, kb = b2.shape
-    if k != kb:
-        raise L.NawsError('naws_gemm_bf16_nt', L.ERR_SHAPE)
-    if out is None:
-        out = torch.empty(((batch, m, n) if batched else (m, n)), device=a.device, dtype=_f32)
-    c2 = out[0] if batched else out
-    sbias = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
-    _chk_batched_aux('naws_gemm_bf16_nt', aux, out, batch)
-    L.call('naws_gemm_bf16_nt', m, n, k, a.data_ptr(), int(a.dtype == torch.bfloat16),
-           a2.stride(0), b.data_ptr(), int(b.dtype == torch.bfloat16), b2.stride(0),
-           out.data_ptr(), c2.stride(0), batch, (a.stride(0) if batched else 0),
-           (b.stride(0) if batched else 0), (out.stride(0) if batched else 0), epilogue,
-           _ptr(bias), sbias, _ptr(aux), (aux.stride(-2) if aux is not None else 0),
-           float(alpha), float(drop_ratio), int(seed) & 0xFFFFFFFFFFFFFFFF, int(accumulate),
-           _stream())
+    batched, batch, m, n, k, lda, ldb, sa, sb = _dense_pair('naws_gemm_bf16_nt', a, b, False, True,
+                                                            (_f32, torch.bfloat16), 'fp32/bf16')
+    out, ldc, sc = _gemm_out(out, batched, batch, m, n, a.device)
+    L.call('naws_gemm_bf16_nt', m, n, k, a.data_ptr(), int(a.dtype == torch.bfloat16), lda,
+           b.data_ptr(), int(b.dtype == torch.bfloat16), ldb, out.data_ptr(), ldc, batch, sa, sb, sc,
+           *_epilogue_tail('naws_gemm_bf16_nt', out, batch, epilogue, bias, aux, alpha, drop_ratio,
+                           seed, accumulate), _stream())
     return out
 
 
 def transpose_to_bf16(x, rows_pad=None, out=None):
     """fp32 [rows, cols] (or [b, rows, cols], batch-contiguous) -> bf16 [cols, rows_pad]."""
-    batched = x.dim() == 3
-    x2 = x[0] if batched else x
-    batch = x.shape[0] if batched else 1
-    rows, cols = x2.shape
-    if x2.stride(1) != 1 or (batched and x.stride(0) != rows * x2.stride(0)):
+    batched, batch, rows, cols, ld, stride = _split_source(x, check=False)
+    if x.stride(-1) != 1 or (batched and stride != rows * ld):
         raise TypeError('x must be row-major with batch stride rows*ld')
     rp = rows_pad if rows_pad is not None else (rows + 7) // 8 * 8
     shape = (batch, cols, rp) if batched else (cols, rp)
     y = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.bfloat16)
-    L.call('naws_transpose_to_bf16', x.data_ptr(), batch, rows, cols, x2.stride(0), rp,
-           y.data_ptr(), _stream())
+    L.call('naws_transpose_to_bf16', x.data_ptr(), batch, rows, cols, ld, rp, y.data_ptr(), _stream())
     return y
 
 
@@ -725,7 +732,7 @@ def conv3x3_nhwc_bf16(x, w_packed, bias, dilation=1, relu=True, out=None):
     _chk(x, 'x'); _chk(w_packed, 'w_packed')
     n, h, w, cin = x.shape
     cout = w_packed.shape[0]
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
+    y = _conv_out(out, (n, h, w, cout), x.device)
     L.call('naws_conv3x3_nhwc_bf16_fwd', x.data_ptr(), w_packed.data_ptr(), _ptr(bias), n, h, w,
            cin, cout, dilation, int(relu), y.data_ptr(), _stream())
     return y
@@ -743,10 +750,7 @@ def conv3x3_nhwc_bf16_wp(x, w_slab, bias, dilation=1, relu=True, out=None, pool2
     cout = w_slab.shape[1]
     if w_slab.shape[0] * 16 != 9 * cin:
         raise ValueError('weight slab K does not match 9 * Cin')
-    shape = (n, h // 2, w // 2, cout) if pool2 else (n, h, w, cout)
-    y = out if out is not None else torch.empty(shape, device=x.device, dtype=_f32)
-    if tuple(y.shape) != shape or y.dtype != _f32 or not y.is_contiguous():
-        raise TypeError('out must be a contiguous fp32 %s tensor' % (shape,))
+    y = _conv_out(out, (n, h // 2, w // 2, cout) if pool2 else (n, h, w, cout), x.device, check=True)
     L.call('naws_conv3x3_nhwc_bf16_wp_fwd', x.data_ptr(), w_slab.data_ptr(), _ptr(bias), n, h, w,
            cin, cout, dilation, int(relu), int(pool2), y.data_ptr(), _stream())
     return y
@@ -756,18 +760,13 @@ def split_bf16x3(x, transpose=False, out=None):
     """fp32 [rows, cols] or [b, rows, cols] (last dim contiguous) -> bf16 planes
     [3, (b,) K/16, outer, 16] ("K-slab-major"): outer/K = rows/cols, or cols/rows when
     `transpose`; K is rounded up to 16 (zero-filled).  x == P[0] + P[1] + P[2] exactly."""
-    batched = x.dim() == 3
-    x2 = x[0] if batched else x
-    if not x.is_cuda or x.dtype != _f32 or x2.stride(1) != 1:
-        raise TypeError('x must be a HIP fp32 tensor with a contiguous last dim')
-    batch = x.shape[0] if batched else 1
-    rows, cols = x2.shape
+    batched, batch, rows, cols, ld, stride = _split_source(x)
     outer, k = (cols, rows) if transpose else (rows, cols)
     kpad = (k + 15) // 16 * 16
     shape = (3, batch, kpad // 16, outer, 16) if batched else (3, kpad // 16, outer, 16)
     p = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.bfloat16)
-    L.call('naws_split_bf16x3', x.data_ptr(), batch, rows, cols, x2.stride(0),
-           (x.stride(0) if batched else 0), int(transpose), kpad, p.data_ptr(), _stream())
+    L.call('naws_split_bf16x3', x.data_ptr(), batch, rows, cols, ld, stride, int(transpose), kpad,
+           p.data_ptr(), _stream())
     return p
 
 
@@ -781,14 +780,11 @@ def conv3x3_nhwc_f32x3(x, w3, bias, dilation=1, relu=True, out=None, pool2=False
     if w3.dtype != torch.bfloat16 or w3.shape[0] != 3 or w3.shape[1] * 16 != 9 * cin:
         raise TypeError('w3 must be the bf16 planes [3, 9*Cin/16, Cout, 16] of the packed weight')
     if pool2:
-        shape = (n, h // 2, w // 2, cout)
-        y = out if out is not None else torch.empty(shape, device=x.device, dtype=_f32)
-        if tuple(y.shape) != shape or y.dtype != _f32 or not y.is_contiguous():
-            raise TypeError('out must be a contiguous fp32 %s tensor' % (shape,))
+        y = _conv_out(out, (n, h // 2, w // 2, cout), x.device, check=True)
         L.call('naws_conv3x3_nhwc_f32x3_pool_fwd', x.data_ptr(), w3.data_ptr(), _ptr(bias), n, h, w,
                cin, cout, int(relu), y.data_ptr(), _stream())
         return y
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
+    y = _conv_out(out, (n, h, w, cout), x.device)
     L.call('naws_conv3x3_nhwc_f32x3_fwd', x.data_ptr(), w3.data_ptr(), _ptr(bias), n, h, w, cin,
            cout, dilation, int(relu), y.data_ptr(), _stream())
     return y
@@ -802,7 +798,7 @@ def conv3x3_winograd_nhwc_f32x3(x, u3, bias, dilation=1, relu=True, out=None, wo
     cout = u3.shape[-2]
     if u3.dtype != torch.bfloat16 or tuple(u3.shape[:3]) != (3, 16, cin // 16):
         raise TypeError('u3 must be the bf16 planes [3, 16, Cin/16, Cout, 16] of U')
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
+    y = _conv_out(out, (n, h, w, cout), x.device)
     nws = L.load().naws_winograd_f32x3_workspace_floats(n, h, w, cin, cout, dilation)
     ws = _workspace(workspace, nws, x.device, 'naws_winograd_f32x3_workspace_floats')
     L.call('naws_conv3x3_winograd_nhwc_f32x3_fwd', x.data_ptr(), u3.data_ptr(), _ptr(bias), n, h,
@@ -842,8 +838,7 @@ def conv3x3_nhwc_f16x2(x, w2, bias, relu=True, out=None, amax_in=None, in_mul=1.
         raise TypeError('w2 must hold the f16 planes [2, 9*Cin/16, Cout, 16] of the packed weight')
     if amax_in is None:
         amax_in, in_mul, in_add = amax_word(x), 1.0, 0.0
-    shape = (n, h // 2, w // 2, cout) if pool2 else (n, h, w, cout)
-    y = out if out is not None else torch.empty(shape, device=x.device, dtype=_f32)
+    y = _conv_out(out, (n, h // 2, w // 2, cout) if pool2 else (n, h, w, cout), x.device)
     L.call('naws_conv3x3_nhwc_f16x2_fwd', x.data_ptr(), w2.planes.data_ptr(),
            w2.inv_scale.data_ptr(), _ptr(bias), n, h, w, cin, cout, int(dilation), int(relu),
            y.data_ptr(),
@@ -877,7 +872,7 @@ def conv3x3_winograd_nhwc_f16x2(x, u2, bias, dilation=1, relu=True, out=None, am
             col or tuple(u2.planes.shape[:3]) in ((2, 16, cin // 16), (2, 36, cin // 16))):
         raise TypeError('u2 must hold the f16 planes [2, 16, Cin/16, Cout, 16] of U (or the '
                         'column form [2, 4, 4 Cin/16, Cout, 16])')
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=_f32)
+    y = _conv_out(out, (n, h, w, cout), x.device)
     if tuple(u2.planes.shape[:3]) == (2, 36, cin // 16):          # winograd4_weight_transform
         nws = L.load().naws_winograd4_f16x2_workspace_floats(n, h, w, cin, cout, dilation)
         ws = _workspace(workspace, nws, x.device, 'naws_winograd4_f16x2_workspace_floats')
@@ -1001,18 +996,13 @@ def min_entropy_loss_grad(x, l, dy):
 def to_bf16_slab(x, transpose=False, out=None):
     """fp32 [rows, cols] or [b, rows, cols] -> bf16 [(b,) K/16, outer, 16] (K-slab-major, K
     rounded up to 64 and zero-filled): the operand layout of gemm_bf16_slab_nt."""
-    batched = x.dim() == 3
-    x2 = x[0] if batched else x
-    if not x.is_cuda or x.dtype != _f32 or x2.stride(1) != 1:
-        raise TypeError('x must be a HIP fp32 tensor with a contiguous last dim')
-    batch = x.shape[0] if batched else 1
-    rows, cols = x2.shape
+    batched, batch, rows, cols, ld, stride = _split_source(x)
     outer, k = (cols, rows) if transpose else (rows, cols)
     kpad = (k + 63) // 64 * 64
     shape = (batch, kpad // 16, outer, 16) if batched else (kpad // 16, outer, 16)
     p = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.bfloat16)
-    L.call('naws_to_bf16_slab', x.data_ptr(), batch, rows, cols, x2.stride(0),
-           (x.stride(0) if batched else 0), int(transpose), kpad, p.data_ptr(), _stream())
+    L.call('naws_to_bf16_slab', x.data_ptr(), batch, rows, cols, ld, stride, int(transpose), kpad,
+           p.data_ptr(), _stream())
     return p
 
 
@@ -1021,25 +1011,15 @@ def gemm_bf16_slab_nt(a, b, out=None, epilogue=L.EPI_NONE, bias=None, aux=None, 
     """C[M,N] (+)= A B^T for bf16 slab operands a [(b,)K/16,M,16], b [(b,)K/16,N,16]
     (to_bf16_slab); bf16 MFMA, fp32 accumulate.  Row-sliced views (a[..., r0:r1, :]) are fine."""
     batched = a.dim() == 4
-    for t in (a, b):
-        if (not t.is_cuda or t.dtype != torch.bfloat16 or t.shape[-1] != 16 or t.stride(-1) != 1
-                or t.stride(-2) != 16):
-            raise TypeError('operands must be bf16 slab tensors [..., K/16, rows, 16]')
-    batch = a.shape[0] if batched else 1
-    mm, k = a.shape[-2], a.shape[-3] * 16
-    nn, kb = b.shape[-2], b.shape[-3] * 16
+    (pa, slab_a, _, sa, mm, k), (pb, slab_b, _, sb, nn, kb) = (_planes(t, torch.bfloat16, 0, batched)
+                                                               for t in (a, b))
     if k != kb:
         raise L.NawsError('naws_gemm_bf16_slab_nt', L.ERR_SHAPE)
-    if out is None:
-        out = torch.empty(((batch, mm, nn) if batched else (mm, nn)), device=a.device, dtype=_f32)
-    c2 = out[0] if batched else out
-    sbias = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
-    _chk_batched_aux('naws_gemm_bf16_slab_nt', aux, out, batch)
-    L.call('naws_gemm_bf16_slab_nt', mm, nn, k, a.data_ptr(), a.stride(-3), b.data_ptr(),
-           b.stride(-3), out.data_ptr(), c2.stride(0), batch, (a.stride(0) if batched else 0),
-           (b.stride(0) if batched else 0), (out.stride(0) if batched else 0), epilogue,
-           _ptr(bias), sbias, _ptr(aux), (aux.stride(-2) if aux is not None else 0), float(alpha),
-           float(drop_ratio), int(seed) & 0xFFFFFFFFFFFFFFFF, int(accumulate), _stream())
+    batch = a.shape[0] if batched else 1
+    out, ldc, sc = _gemm_out(out, batched, batch, mm, nn, a.device)
+    L.call('naws_gemm_bf16_slab_nt', mm, nn, k, pa, slab_a, pb, slab_b, out.data_ptr(), ldc, batch,
+           sa, sb, sc, *_epilogue_tail('naws_gemm_bf16_slab_nt', out, batch, epilogue, bias, aux,
+                                       alpha, drop_ratio, seed, accumulate), _stream())
     return out
 
 
@@ -1056,26 +1036,16 @@ def gemm_f32x3_nt(a3, b3, out=None, epilogue=L.EPI_NONE, bias=None, aux=None, al
     (split_bf16x3); fp32-accurate, runs on the bf16 MFMA.  Row-sliced plane views
     (a3[..., r0:r1, :]) are fine."""
     batched = a3.dim() == 5
-    for t in (a3, b3):
-        if (not t.is_cuda or t.dtype != torch.bfloat16 or t.shape[0] != 3 or t.shape[-1] != 16
-                or t.stride(-1) != 1 or t.stride(-2) != 16):
-            raise TypeError('operands must be bf16 split planes [3, ..., K/16, rows, 16]')
-    batch = a3.shape[1] if batched else 1
-    mm, k = a3.shape[-2], a3.shape[-3] * 16
-    nn, kb = b3.shape[-2], b3.shape[-3] * 16
+    (pa, slab_a, plane_a, sa, mm, k), (pb, slab_b, plane_b, sb, nn, kb) = (
+        _planes(t, torch.bfloat16, 3, batched) for t in (a3, b3))
     if k != kb:
         raise L.NawsError('naws_gemm_f32x3_nt', L.ERR_SHAPE)
-    if out is None:
-        out = torch.empty(((batch, mm, nn) if batched else (mm, nn)), device=a3.device, dtype=_f32)
-    c2 = out[0] if batched else out
-    sbias = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
-    _chk_batched_aux('naws_gemm_f32x3_nt', aux, out, batch)
-    L.call('naws_gemm_f32x3_nt', mm, nn, k, a3.data_ptr(), a3.stride(-3), a3.stride(0),
-           b3.data_ptr(), b3.stride(-3), b3.stride(0), out.data_ptr(), c2.stride(0), batch,
-           (a3.stride(1) if batched else 0), (b3.stride(1) if batched else 0),
-           (out.stride(0) if batched else 0), epilogue, _ptr(bias), sbias, _ptr(aux),
-           (aux.stride(-2) if aux is not None else 0), float(alpha), float(drop_ratio),
-           int(seed) & 0xFFFFFFFFFFFFFFFF, int(accumulate), _stream())
+    batch = a3.shape[1] if batched else 1
+    out, ldc, sc = _gemm_out(out, batched, batch, mm, nn, a3.device)
+    L.call('naws_gemm_f32x3_nt', mm, nn, k, pa, slab_a, plane_a, pb, slab_b, plane_b, out.data_ptr(),
+           ldc, batch, sa, sb, sc,
+           *_epilogue_tail('naws_gemm_f32x3_nt', out, batch, epilogue, bias, aux, alpha, drop_ratio,
+                           seed, accumulate), _stream())
     return out
 
 
@@ -1104,12 +1074,7 @@ def split_f16x2(x, transpose=False, out=None, rowmul=None):
     [2, (b,) K/16, outer, 16] (K rounded up to 32, zero-filled) scaled per outer index by a
     power of two that puts the row maximum in [2^14, 2^15):  x * s = hi + lo to 22+ bits.
     rowmul (fp32 [rows], optional): split diag(rowmul) x instead."""
-    batched = x.dim() == 3
-    x2 = x[0] if batched else x
-    if not x.is_cuda or x.dtype != _f32 or x2.stride(1) != 1:
-        raise TypeError('x must be a HIP fp32 tensor with a contiguous last dim')
-    batch = x.shape[0] if batched else 1
-    rows, cols = x2.shape
+    batched, batch, rows, cols, ld, stride = _split_source(x)
     outer, k = (cols, rows) if transpose else (rows, cols)
     kpad = (k + 31) // 32 * 32
     if out is None:
@@ -1120,9 +1085,8 @@ def split_f16x2(x, transpose=False, out=None, rowmul=None):
     if rowmul is not None and (rowmul.numel() != rows or rowmul.dtype != _f32
                                or not rowmul.is_contiguous()):
         raise TypeError('rowmul must be a contiguous fp32 vector with one entry per source row')
-    L.call('naws_split_f16x2_kscaled', x.data_ptr(), batch, rows, cols, x2.stride(0),
-           (x.stride(0) if batched else 0), int(transpose), kpad, out.planes.data_ptr(),
-           out.scales.data_ptr(), _ptr(rowmul), _stream())
+    L.call('naws_split_f16x2_kscaled', x.data_ptr(), batch, rows, cols, ld, stride, int(transpose),
+           kpad, out.planes.data_ptr(), out.scales.data_ptr(), _ptr(rowmul), _stream())
     return out
 
 
@@ -1132,33 +1096,21 @@ def gemm_f32_f16x2_nt(a, b, out=None, epilogue=L.EPI_NONE, bias=None, aux=None, 
     """C[M,N] (+)= A B^T from F16x2 operands (split_f16x2); fp32 in / fp32 accumulate / fp32 out
     on the f16 MFMA with three products per K-slab.  Row-sliced operands (`.rows`) are fine.
     rowmax / rowmax_seg / colmax / colmax_rowmul: as `gemm`."""
-    a3, b3 = a.planes, b.planes
-    batched = a3.dim() == 5
-    for t in (a3, b3):
-        if (not t.is_cuda or t.dtype != torch.float16 or t.shape[0] != 2 or t.shape[-1] != 16
-                or t.stride(-1) != 1 or t.stride(-2) != 16):
-            raise TypeError('operands must be f16 split planes [2, ..., K/16, rows, 16]')
+    batched = a.planes.dim() == 5
+    (pa, slab_a, plane_a, spa, mm, k), (pb, slab_b, plane_b, spb, nn, kb) = (
+        _planes(t.planes, torch.float16, 2, batched) for t in (a, b))
     sa, sb = a.inv_scale, b.inv_scale
     if sa.stride(-1) != 1 or sb.stride(-1) != 1:
         raise TypeError('scale vectors must be contiguous')
-    batch = a3.shape[1] if batched else 1
-    mm, k = a3.shape[-2], a3.shape[-3] * 16
-    nn, kb = b3.shape[-2], b3.shape[-3] * 16
     if k != kb:
         raise L.NawsError('naws_gemm_f32_f16x2_nt', L.ERR_SHAPE)
-    if out is None:
-        out = torch.empty(((batch, mm, nn) if batched else (mm, nn)), device=a3.device, dtype=_f32)
-    c2 = out[0] if batched else out
-    sbias = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
-    _chk_batched_aux('naws_gemm_f32_f16x2_nt_amax', aux, out, batch)
-    L.call('naws_gemm_f32_f16x2_nt_amax', mm, nn, k, a3.data_ptr(), a3.stride(-3), a3.stride(0),
-           sa.data_ptr(), b3.data_ptr(), b3.stride(-3), b3.stride(0), sb.data_ptr(),
-           out.data_ptr(), c2.stride(0), batch,
-           (a3.stride(1) if batched else 0), (b3.stride(1) if batched else 0),
-           (out.stride(0) if batched else 0), (sa.stride(0) if batched else 0),
-           (sb.stride(0) if batched else 0), epilogue, _ptr(bias), sbias, _ptr(aux),
-           (aux.stride(-2) if aux is not None else 0), float(alpha), float(drop_ratio),
-           int(seed) & 0xFFFFFFFFFFFFFFFF, int(accumulate),
+    batch = a.planes.shape[1] if batched else 1
+    out, ldc, sc = _gemm_out(out, batched, batch, mm, nn, a.planes.device)
+    L.call('naws_gemm_f32_f16x2_nt_amax', mm, nn, k, pa, slab_a, plane_a, sa.data_ptr(), pb, slab_b,
+           plane_b, sb.data_ptr(), out.data_ptr(), ldc, batch, spa, spb, sc,
+           (sa.stride(0) if batched else 0), (sb.stride(0) if batched else 0),
+           *_epilogue_tail('naws_gemm_f32_f16x2_nt_amax', out, batch, epilogue, bias, aux, alpha,
+                           drop_ratio, seed, accumulate),
            *_amax_args(rowmax, rowmax_seg, colmax, colmax_rowmul), _stream())
     return out
 
@@ -1171,19 +1123,13 @@ def gemm_f32_f16x2_nt_cols(a, b, out, col0, width, epilogue=L.EPI_NONE, bias=Non
     of the range's rowmax segment.  Element (m, c) draws the Dropout counter m * width + col0 + c,
     as the full-width gemm_f32_f16x2_nt does: the pieces of one activation are bit-identical to
     the single launch (naws_gemm_f32_f16x2_nt_cols)."""
-    a3, b3 = a.planes, b.planes
-    for t in (a3, b3):
-        if (not t.is_cuda or t.dtype != torch.float16 or t.dim() != 4 or t.shape[0] != 2
-                or t.shape[-1] != 16 or t.stride(-1) != 1 or t.stride(-2) != 16):
-            raise TypeError('operands must be unbatched f16 split planes [2, K/16, rows, 16]')
-    sa, sb = a.inv_scale, b.inv_scale
-    mm, k = a3.shape[-2], a3.shape[-3] * 16
-    nn = b3.shape[-2]
-    if k != b3.shape[-3] * 16 or out.shape != (mm, nn) or out.stride(1) != 1:
+    (pa, slab_a, plane_a, _, mm, k), (pb, slab_b, plane_b, _, nn, kb) = (
+        _planes(t.planes, torch.float16, 2, None) for t in (a, b))
+    if k != kb or out.shape != (mm, nn) or out.stride(1) != 1:
         raise L.NawsError('naws_gemm_f32_f16x2_nt_cols', L.ERR_SHAPE)
-    L.call('naws_gemm_f32_f16x2_nt_cols', mm, nn, k, a3.data_ptr(), a3.stride(-3), a3.stride(0),
-           sa.data_ptr(), b3.data_ptr(), b3.stride(-3), b3.stride(0), sb.data_ptr(), out.data_ptr(),
-           out.stride(0), epilogue, _ptr(bias), float(drop_ratio), int(seed) & 0xFFFFFFFFFFFFFFFF,
+    L.call('naws_gemm_f32_f16x2_nt_cols', mm, nn, k, pa, slab_a, plane_a, a.inv_scale.data_ptr(), pb,
+           slab_b, plane_b, b.inv_scale.data_ptr(), out.data_ptr(), out.stride(0), epilogue,
+           _ptr(bias), float(drop_ratio), int(seed) & 0xFFFFFFFFFFFFFFFF,
            *_amax_args(rowmax, rowmax_seg, colmax, None)[:3], int(width), int(col0), _stream())
     return out
 
@@ -1195,23 +1141,18 @@ def gemm_f32_f16x2_nt_xk(a, x, out=None, ncols=None, scale_x=None):
     kernel's transposing LDS reads, so no transposed copy of x is made.  x's per-row scales are
     NOT applied (the caller folds them into a, as the fc6 wgrad does with rowmul); scale_x:
     optional per-column factors.  ncols: (c0, c1) restricts to x's columns c0..c1 (multiples of 16)."""
-    a3, x3 = a.planes, x.planes
-    for t in (a3, x3):
-        if (not t.is_cuda or t.dtype != torch.float16 or t.dim() != 4 or t.shape[0] != 2
-                or t.shape[-1] != 16 or t.stride(-1) != 1 or t.stride(-2) != 16):
-            raise TypeError('operands must be unbatched f16 split planes [2, K/16, rows, 16]')
-    mm, k = a3.shape[-2], a3.shape[-3] * 16
-    r, n_all = x3.shape[-2], x3.shape[-3] * 16
+    x3 = x.planes
+    (pa, slab_a, plane_a, _, mm, k), (_, slab_x, plane_x, _, r, n_all) = (
+        _planes(t, torch.float16, 2, None) for t in (a.planes, x3))      # (x's "K" axis: its columns)
     c0, c1 = (0, n_all) if ncols is None else ncols
     if c0 % 16 or c1 % 16 or not 0 <= c0 < c1 <= n_all or r > k:
         raise L.NawsError('naws_gemm_f32_f16x2_nt_xk', L.ERR_SHAPE)
     nn = c1 - c0
     if out is None:
-        out = torch.empty((mm, nn), device=a3.device, dtype=_f32)
-    xs = x3[:, c0 // 16:]
-    L.call('naws_gemm_f32_f16x2_nt_xk', mm, nn, k, a3.data_ptr(), a3.stride(-3), a3.stride(0),
-           a.inv_scale.data_ptr(), xs.data_ptr(), x3.stride(-3), x3.stride(0), r,
-           _ptr(scale_x), out.data_ptr(), out.stride(0), _stream())
+        out = torch.empty((mm, nn), device=a.planes.device, dtype=_f32)
+    L.call('naws_gemm_f32_f16x2_nt_xk', mm, nn, k, pa, slab_a, plane_a, a.inv_scale.data_ptr(),
+           x3[:, c0 // 16:].data_ptr(), slab_x, plane_x, r, _ptr(scale_x), out.data_ptr(),
+           out.stride(0), _stream())
     return out
 
 
@@ -1223,13 +1164,9 @@ def gemm_f32_f16x2_nt_xk_sgd(a, x, param, momentum_buf, lr, lr_mult, weight_deca
     writes param's own operand planes `wplanes` (F16x2 planes [2, N_all/16, M_all, 16]).  rows =
     (r0, r1): a's rows are rows r0..r1 of param; ncols as in gemm_f32_f16x2_nt_xk.  bound / rowmax
     (int32 [M_all]) / inv_scale (fp32 [M_all]) / overflow as acm_sgd_update_f16x2."""
-    a3, x3 = a.planes, x.planes
-    for t in (a3, x3, wplanes):
-        if (not t.is_cuda or t.dtype != torch.float16 or t.dim() != 4 or t.shape[0] != 2
-                or t.shape[-1] != 16 or t.stride(-1) != 1 or t.stride(-2) != 16):
-            raise TypeError('operands must be unbatched f16 split planes [2, K/16, rows, 16]')
-    mm, k = a3.shape[-2], a3.shape[-3] * 16
-    r, n_all = x3.shape[-2], x3.shape[-3] * 16
+    x3 = x.planes
+    (pa, slab_a, plane_a, _, mm, k), (_, slab_x, plane_x, _, r, n_all), _ = (
+        _planes(t, torch.float16, 2, None) for t in (a.planes, x3, wplanes))
     c0, c1 = (0, n_all) if ncols is None else ncols
     r0, r1 = (0, mm) if rows is None else rows
     if (c0 % 16 or c1 % 16 or not 0 <= c0 < c1 <= n_all or r > k or r1 - r0 != mm
@@ -1241,14 +1178,12 @@ def gemm_f32_f16x2_nt_xk_sgd(a, x, param, momentum_buf, lr, lr_mult, weight_deca
     for t, dt in ((bound, torch.int32), (rowmax, torch.int32), (inv_scale, _f32)):
         if t.dtype != dt or t.numel() != param.shape[0] or not t.is_contiguous():
             raise TypeError('bound / rowmax / inv_scale: contiguous [rows] int32 / int32 / fp32')
-    xs = x3[:, c0 // 16:]
-    ws = wplanes[:, c0 // 16:, r0:]
-    L.call('naws_gemm_f32_f16x2_nt_xk_sgd', mm, c1 - c0, k, a3.data_ptr(), a3.stride(-3), a3.stride(0),
-           a.inv_scale.data_ptr(), xs.data_ptr(), x3.stride(-3), x3.stride(0), r, None,
+    L.call('naws_gemm_f32_f16x2_nt_xk_sgd', mm, c1 - c0, k, pa, slab_a, plane_a,
+           a.inv_scale.data_ptr(), x3[:, c0 // 16:].data_ptr(), slab_x, plane_x, r, None,
            param[r0:r1, c0:c1].data_ptr(), momentum_buf[r0:r1, c0:c1].data_ptr(), param.stride(0),
            lr.data_ptr(), float(lr_mult), float(weight_decay), float(momentum), int(nesterov),
-           int(gpu_num), int(iter_count), ws.data_ptr(), wplanes.stride(0), wplanes.shape[2],
-           bound[r0:].data_ptr(), rowmax[r0:].data_ptr(), inv_scale[r0:].data_ptr(),
+           int(gpu_num), int(iter_count), wplanes[:, c0 // 16:, r0:].data_ptr(), wplanes.stride(0),
+           wplanes.shape[2], bound[r0:].data_ptr(), rowmax[r0:].data_ptr(), inv_scale[r0:].data_ptr(),
            overflow.data_ptr(), int(overflow_tag), _stream())
 
 
@@ -1258,21 +1193,17 @@ def gemm_bf16_slab_nt_sgd(a, b, param, momentum_buf, lr, lr_mult, weight_decay, 
     [M_all, N] row-major view of the arena; `momentum_buf` likewise) instead of storing the
     gradient a b^T, and rounds the updated rows into param's own bf16 operand plane `wplane`
     ([N/16, M_all, 16], to_bf16_slab(param))."""
-    for t in (a, b, wplane):
-        if (not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 3 or t.shape[-1] != 16
-                or t.stride(-1) != 1 or t.stride(-2) != 16):
-            raise TypeError('operands must be unbatched bf16 slab tensors [K/16, rows, 16]')
-    mm, k = a.shape[-2], a.shape[-3] * 16
-    n = b.shape[-2]
+    (pa, slab_a, _, _, mm, k), (pb, slab_b, _, _, n, kb), _ = (
+        _planes(t, torch.bfloat16, 0, None) for t in (a, b, wplane))
     r0, r1 = (0, mm) if rows is None else rows
-    if (b.shape[-3] * 16 != k or r1 - r0 != mm or param.dim() != 2 or param.shape[1] != n
+    if (kb != k or r1 - r0 != mm or param.dim() != 2 or param.shape[1] != n
             or param.stride(1) != 1 or momentum_buf.shape != param.shape
             or momentum_buf.stride() != param.stride() or wplane.shape[0] * 16 < n
             or wplane.shape[1] != param.shape[0] or not wplane.is_contiguous()
             or not 0 <= r0 < r1 <= param.shape[0]):
         raise L.NawsError('naws_gemm_bf16_slab_nt_sgd', L.ERR_SHAPE)
-    L.call('naws_gemm_bf16_slab_nt_sgd', mm, n, k, a.data_ptr(), a.stride(-3), b.data_ptr(),
-           b.stride(-3), momentum_buf[r0:r1].data_ptr(), param[r0:r1].data_ptr(), param.stride(0),
+    L.call('naws_gemm_bf16_slab_nt_sgd', mm, n, k, pa, slab_a, pb, slab_b,
+           momentum_buf[r0:r1].data_ptr(), param[r0:r1].data_ptr(), param.stride(0),
            lr.data_ptr(), float(lr_mult), float(weight_decay), float(momentum), int(nesterov),
            int(gpu_num), int(iter_count), wplane[:, r0:].data_ptr(), wplane.shape[1], _stream())
 
@@ -1294,12 +1225,7 @@ def split_f16x2_dual(x, scales_n=None, scales_t=None, rowmul=None, out_n=None, o
     column-scaled transposed planes of diag(rowmul) x (outer = cols, K = rows) when `scales_t` is
     given.  scales_* are `amax_scales` blocks whose [0] already holds the maxima (bit patterns)
     reported by the GEMM that produced x.  Returns (normal or None, transposed or None)."""
-    batched = x.dim() == 3
-    x2 = x[0] if batched else x
-    if not x.is_cuda or x.dtype != _f32 or x2.stride(1) != 1:
-        raise TypeError('x must be a HIP fp32 tensor with a contiguous last dim')
-    batch = x.shape[0] if batched else 1
-    rows, cols = x2.shape
+    batched, batch, rows, cols, ld, stride = _split_source(x)
     kn, kt = (cols + 31) // 32 * 32, (rows + 31) // 32 * 32
     bs = (batch,) if batched else ()
     pn = pt = None
@@ -1321,8 +1247,8 @@ def split_f16x2_dual(x, scales_n=None, scales_t=None, rowmul=None, out_n=None, o
     if rowmul is not None and (rowmul.numel() != rows or rowmul.dtype != _f32
                                or not rowmul.is_contiguous()):
         raise TypeError('rowmul must be a contiguous fp32 vector with one entry per source row')
-    L.call('naws_split_f16x2_dual', x.data_ptr(), batch, rows, cols, x2.stride(0),
-           (x.stride(0) if batched else 0), _ptr(scales_n), _ptr(scales_t), _ptr(rowmul),
+    L.call('naws_split_f16x2_dual', x.data_ptr(), batch, rows, cols, ld, stride, _ptr(scales_n),
+           _ptr(scales_t), _ptr(rowmul),
            _ptr(pn.planes if pn else None), _ptr(scales_n), kn,
            _ptr(pt.planes if pt else None), _ptr(scales_t), kt, _stream())
     return pn, pt
@@ -1557,13 +1483,10 @@ def split_f16x2_rows_if(x, rowmax, out, cond, cond_value):
     """Redo the row-scaled planes of x (fp32 [rows, cols] or [b, rows, cols]) into the F16x2 `out`
     from the maxima `rowmax` (int32 bit patterns, [b*rows]) - only if cond[0] == cond_value when
     the kernel runs."""
-    batched = x.dim() == 3
-    x2 = x[0] if batched else x
-    batch = x.shape[0] if batched else 1
-    rows, cols = x2.shape
-    L.call('naws_split_f16x2_rows_if', x.data_ptr(), batch, rows, cols, x2.stride(0),
-           (x.stride(0) if batched else 0), rowmax.data_ptr(), out.planes.data_ptr(),
-           out.inv_scale.data_ptr(), (cols + 31) // 32 * 32, _ptr(cond), int(cond_value), _stream())
+    _, batch, rows, cols, ld, stride = _split_source(x, check=False)
+    L.call('naws_split_f16x2_rows_if', x.data_ptr(), batch, rows, cols, ld, stride, rowmax.data_ptr(),
+           out.planes.data_ptr(), out.inv_scale.data_ptr(), (cols + 31) // 32 * 32, _ptr(cond),
+           int(cond_value), _stream())
     return out
 
 

@@ -99,6 +99,40 @@ def test_argument_validation_happens_before_any_launch():
     assert L.naws_min_entropy_loss_bwd(a, a, none, 2, 4, a, none) == lib.ERR_NULL
 
 
+def test_validation_codes_equal_the_recorded_parent():
+    """The GEMM / conv3x3 entry points behind csrc/entry_args.h return, for every single violated
+    condition and every pair of them, the code the library returned before the front end was
+    shared (tests/golden/cabi_validation_before.json; cases from make_cabi_validation.py, none of
+    which reaches a launch)."""
+    import json
+    import sys
+    from naws_hip import lib
+    sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
+    try:
+        import make_cabi_validation as gen
+    finally:
+        sys.path.pop(0)
+    L = lib.load()
+    rec = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'cabi_validation_before.json')))
+    tab = gen.table()
+    ptrs = gen.Pointers()
+    assert sorted(rec) == sorted(tab) == ['conv', 'gemm']
+    assert len(rec['gemm']) + len(rec['conv']) >= 13
+    four = {lib.ERR_SHAPE, lib.ERR_ARG, lib.ERR_NULL, lib.ERR_UNSUPPORTED}
+    for fam, fns in tab.items():
+        assert sorted(rec[fam]) == sorted(fns)
+        seen = set()
+        for fn, case_list in fns.items():
+            e = rec[fam][fn]
+            assert e['n'] == len(case_list) == len(e['codes']) and e['cases_sha1'] == gen.digest(case_list), fn
+            want = [-int(c) for c in e['codes']]
+            got = [getattr(L, fn)(*ptrs.resolve(args)) for _, args in case_list]
+            diff = [(l, g, w) for (l, _), g, w in zip(case_list, got, want) if g != w]
+            assert not diff, (fn, diff[:8])
+            seen |= set(want)
+        assert seen == four, (fam, seen)       # a one-code table would pass vacuously
+
+
 def test_process_wide_state_entry_points():
     """include/naws.h lists the library's only process-wide state: the per-(kernel, device)
     launch-attribute record (resettable) and the A/B knobs (unknown knob = NAWS_ERR_ARG);

@@ -235,6 +235,15 @@ int naws_conv3x3_nhwc_wgrad(const float* X, const float* dY, int N, int H, int W
  * (batch_idx, x1, y1, x2, y2) in input-image pixels.  Y: [R,C,ph,pw].
  * argmax (int32, same shape as Y, value h*W+w or -1) may be NULL.
  * boost may be NULL; otherwise [R] and Y[r,...] *= boost[r] (fused a-3).
+ * Every ph x pw runs, in either layout, with or without argmax: the NHWC
+ * kernels stage their output in LDS (160 KB per workgroup; a launch above
+ * 64 KB has the kernel's dynamic-LDS limit raised first), and where the tile
+ * of the general kernel does not fit (ph*pw > 160, > 80 with argmax) it
+ * writes Y without staging - the same values.  The operand-writing and
+ * hierarchical entries below (naws_roi_pool_f_f16x2*_fwd,
+ * naws_roi_pool_f_nhwc_hier_fwd, naws_roi_pool_f_bf16_slab_mapped_fwd) accept
+ * ph*pw <= 256 only - two rois of that grid are 131080 bytes of LDS - and
+ * return UNSUPPORTED beyond it, before anything is enqueued.
  * Errors: R<0, C/H/W/ph/pw<=0 -> SHAPE; layout unknown -> ARG.
  * ------------------------------------------------------------------------ */
 int naws_roi_pool_f_fwd(const float* X, int layout, int N, int C, int H, int W,

@@ -44,9 +44,12 @@ __device__ __forceinline__ void bin_range(int p, float bin_size, int roi_start, 
 }
 
 // ---- NHWC: one workgroup = one RoI x CT channels -------------------------
+// STAGED = false: the [CT x bins] tile (and its argmax twin) no longer fits the 160 KB of LDS
+// (PH*PW > 160, or > 80 with argmax): every lane writes its channel's bins straight to Y - the
+// same values, uncoalesced; no geometry is refused.
 constexpr int CT = 256;
 
-template <bool WITH_ARGMAX>
+template <bool WITH_ARGMAX, bool STAGED = true>
 __global__ __launch_bounds__(CT) void roi_pool_nhwc_kernel(
     const float* __restrict__ X, int C, int H, int W, const float* __restrict__ rois,
     const float* __restrict__ boost, int PH, int PW, float spatial_scale,
@@ -97,17 +100,25 @@ __global__ __launch_bounds__(CT) void roi_pool_nhwc_kernel(
         }
       }
       const int bin = ph * PW + pw;
-      tile[threadIdx.x * nb + bin] = best * scale;
-      if (WITH_ARGMAX) itile[threadIdx.x * nb + bin] = besti;
+      if constexpr (STAGED) {
+        tile[threadIdx.x * nb + bin] = best * scale;
+        if (WITH_ARGMAX) itile[threadIdx.x * nb + bin] = besti;
+      } else if (active) {
+        const int64_t o = ((int64_t)r * C + c) * nb + bin;
+        Y[o] = best * scale;
+        if (WITH_ARGMAX) argmax[o] = besti;
+      }
     }
   }
-  __syncthreads();
-  const int nch = min(CT, C - c0);
-  const int count = nch * nb;
-  const int64_t base = ((int64_t)r * C + c0) * nb;
-  for (int i = threadIdx.x; i < count; i += CT) {
-    Y[base + i] = tile[i];
-    if (WITH_ARGMAX) argmax[base + i] = itile[i];
+  if constexpr (STAGED) {
+    __syncthreads();
+    const int nch = min(CT, C - c0);
+    const int count = nch * nb;
+    const int64_t base = ((int64_t)r * C + c0) * nb;
+    for (int i = threadIdx.x; i < count; i += CT) {
+      Y[base + i] = tile[i];
+      if (WITH_ARGMAX) argmax[base + i] = itile[i];
+    }
   }
 }
 
@@ -540,6 +551,18 @@ __global__ void roi_iou_kernel(const float* __restrict__ rois, int n, float* __r
   J[idx] = inters / uni;
 }
 
+// Dynamic LDS of the RoIPoolF launches.  A workgroup may hold 160 KB; a request above 64 KB goes
+// through naws_allow_lds first (misc_ops.hip).  The XCD-sliced kernel stages RG rois x 64 channels
+// x PH*PW bins (+ RG operand scales): with PH*PW <= ROI_FAST_BINS that is at most 65540 bytes for
+// one roi per workgroup and 131080 for the operand writers' two (12x12: 73736, 14x14: 100360).
+constexpr size_t ROI_LDS_MAX = 160 * 1024;
+constexpr int ROI_FAST_BINS = 256;      // PH*PW the plane / slab / hierarchical entries accept
+
+constexpr size_t roi_xcd_lds(int nb, int rg) {
+  return ((size_t)rg * 64 * nb + rg) * sizeof(float);
+}
+static_assert(roi_xcd_lds(ROI_FAST_BINS, 2) <= ROI_LDS_MAX, "two rois of the largest grid fit");
+
 }  // namespace
 
 extern "C" int naws_roi_pool_f_fwd(const float* X, int layout, int N, int C, int H, int W,
@@ -556,24 +579,44 @@ extern "C" int naws_roi_pool_f_fwd(const float* X, int layout, int N, int C, int
   hipStream_t s = (hipStream_t)stream;
   const int nb = pooled_h * pooled_w;
   if (layout == NAWS_LAYOUT_NHWC) {
-    size_t lds = (size_t)CT * nb * sizeof(float) * (argmax ? 2 : 1);
-    if (lds > 160 * 1024) return NAWS_ERR_UNSUPPORTED;
+    // the staged kernel's tile; past the LDS it falls to the unstaged form (every geometry runs)
+    const size_t lds = (size_t)CT * nb * sizeof(float) * (argmax ? 2 : 1);
+    const bool staged = lds <= ROI_LDS_MAX;
     dim3 grid(R, (unsigned)naws_cdiv(C, CT));
-    if (argmax)
-      hipLaunchKernelGGL(roi_pool_nhwc_kernel<true>, grid, dim3(CT), lds, s, X, C, H, W, rois,
-                         boost, pooled_h, pooled_w, spatial_scale, Y, argmax);
-    else if (C % 64 == 0 && ((uintptr_t)X % 16) == 0 && pooled_h * pooled_w <= 256 &&
-             (int64_t)R * (C / 64) < 0x7fffffffLL)
+    if (argmax) {
+      if (staged) {
+        if (lds > 64 * 1024 && naws_allow_lds(roi_pool_nhwc_kernel<true>) != NAWS_OK)
+          return NAWS_ERR_LAUNCH;
+        hipLaunchKernelGGL(roi_pool_nhwc_kernel<true>, grid, dim3(CT), lds, s, X, C, H, W, rois,
+                           boost, pooled_h, pooled_w, spatial_scale, Y, argmax);
+      } else {
+        hipLaunchKernelGGL((roi_pool_nhwc_kernel<true, false>), grid, dim3(CT), 0, s, X, C, H, W,
+                           rois, boost, pooled_h, pooled_w, spatial_scale, Y, argmax);
+      }
+    } else if (C % 64 == 0 && ((uintptr_t)X % 16) == 0 && nb <= ROI_FAST_BINS &&
+               (int64_t)R * (C / 64) < 0x7fffffffLL) {
+      const size_t xl = roi_xcd_lds(nb, 1);
+      if (xl > 64 * 1024 && naws_allow_lds(roi_pool_nhwc_xcd_kernel<false>) != NAWS_OK)
+        return NAWS_ERR_LAUNCH;
       hipLaunchKernelGGL(roi_pool_nhwc_xcd_kernel<false>, dim3((unsigned)(R * (C / 64))), dim3(64),
-                         (size_t)(64 * pooled_h * pooled_w + 1) * sizeof(float), s, X, C, H, W, rois,
-                         R, boost, pooled_h, pooled_w, spatial_scale, C / 64, Y, RoiPlaneOut{});
-    else if (C % 4 == 0 && ((uintptr_t)X % 16) == 0 && pooled_w <= 64)
+                         xl, s, X, C, H, W, rois, R, boost, pooled_h, pooled_w, spatial_scale,
+                         C / 64, Y, RoiPlaneOut{});
+    } else if (C % 4 == 0 && ((uintptr_t)X % 16) == 0 &&
+               (size_t)4 * 64 * pooled_w * sizeof(float) <= ROI_LDS_MAX) {   // one bin row: pw <= 40
+      const size_t vl = (size_t)4 * 64 * pooled_w * sizeof(float);
+      if (vl > 64 * 1024 && naws_allow_lds(roi_pool_nhwc_v4_kernel) != NAWS_OK)
+        return NAWS_ERR_LAUNCH;
       hipLaunchKernelGGL(roi_pool_nhwc_v4_kernel, dim3(R, (unsigned)naws_cdiv(C, 256)), dim3(64),
-                         (size_t)4 * 64 * pooled_w * sizeof(float), s, X, C, H, W, rois, boost,
-                         pooled_h, pooled_w, spatial_scale, Y);
-    else
+                         vl, s, X, C, H, W, rois, boost, pooled_h, pooled_w, spatial_scale, Y);
+    } else if (staged) {
+      if (lds > 64 * 1024 && naws_allow_lds(roi_pool_nhwc_kernel<false>) != NAWS_OK)
+        return NAWS_ERR_LAUNCH;
       hipLaunchKernelGGL(roi_pool_nhwc_kernel<false>, grid, dim3(CT), lds, s, X, C, H, W, rois,
                          boost, pooled_h, pooled_w, spatial_scale, Y, argmax);
+    } else {
+      hipLaunchKernelGGL((roi_pool_nhwc_kernel<false, false>), grid, dim3(CT), 0, s, X, C, H, W,
+                         rois, boost, pooled_h, pooled_w, spatial_scale, Y, argmax);
+    }
   } else {
     int64_t total = (int64_t)R * C * nb;
     int blocks = (int)std::min<int64_t>(naws_cdiv(total, 256), 256 * 32);
@@ -596,16 +639,19 @@ extern "C" int naws_roi_pool_f_f16x2_fwd(const float* X, int N, int C, int H, in
   NAWS_REQUIRE_PTR(X); NAWS_REQUIRE_PTR(rois); NAWS_REQUIRE_PTR(amax_words);
   NAWS_REQUIRE_PTR(planes); NAWS_REQUIRE_PTR(scales);
   const long long K = (long long)C * pooled_h * pooled_w;
-  if (C % 64 != 0 || pooled_h * pooled_w > 256 || K % 32 != 0 || (int64_t)R * (C / 64) >= 0x7fffffffLL)
+  if (C % 64 != 0 || pooled_h * pooled_w > ROI_FAST_BINS || K % 32 != 0 ||
+      (int64_t)R * (C / 64) >= 0x7fffffffLL)
     return NAWS_ERR_UNSUPPORTED;
   if ((((uintptr_t)X | (uintptr_t)planes) & 15) != 0) return NAWS_ERR_ARG;
   RoiPlaneOut po;
   po.P = (unsigned short*)planes; po.inv_scale = scales + R; po.amax_words = (const unsigned*)amax_words;
   po.n_words = n_words; po.plane = K * R; po.R = R; po.bf16 = 0;
-  hipLaunchKernelGGL(roi_pool_nhwc_xcd_kernel<true>, dim3((unsigned)(R * (C / 64))), dim3(64),
-                     (size_t)(64 * pooled_h * pooled_w + 1) * sizeof(float), (hipStream_t)stream, X, C,
-                     H, W, rois, R, boost, pooled_h, pooled_w, spatial_scale, C / 64, (float*)nullptr,
-                     po);
+  const size_t lds = roi_xcd_lds(pooled_h * pooled_w, 1);
+  if (lds > 64 * 1024 && naws_allow_lds(roi_pool_nhwc_xcd_kernel<true>) != NAWS_OK)
+    return NAWS_ERR_LAUNCH;
+  hipLaunchKernelGGL(roi_pool_nhwc_xcd_kernel<true>, dim3((unsigned)(R * (C / 64))), dim3(64), lds,
+                     (hipStream_t)stream, X, C, H, W, rois, R, boost, pooled_h, pooled_w,
+                     spatial_scale, C / 64, (float*)nullptr, po);
   return naws_check_launch();
 }
 
@@ -635,20 +681,47 @@ extern "C" int naws_roi_pool_f_nhwc_hier_fwd(const float* X, int N, int C, int H
     return NAWS_ERR_SHAPE;
   if (R == 0) return NAWS_OK;
   NAWS_REQUIRE_PTR(X); NAWS_REQUIRE_PTR(rois); NAWS_REQUIRE_PTR(Y); NAWS_REQUIRE_PTR(workspace);
-  if (C % 64 != 0 || pooled_h * pooled_w > 256 || (int64_t)R * (C / 64) >= 0x7fffffffLL)
+  if (C % 64 != 0 || pooled_h * pooled_w > ROI_FAST_BINS || (int64_t)R * (C / 64) >= 0x7fffffffLL)
     return NAWS_ERR_UNSUPPORTED;
   if ((((uintptr_t)X | (uintptr_t)workspace) & 15) != 0) return NAWS_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
+  const size_t lds = roi_xcd_lds(pooled_h * pooled_w, 1);       // (before anything is enqueued)
+  if (lds > 64 * 1024 && naws_allow_lds(roi_pool_nhwc_xcd_kernel<false, true, 4>) != NAWS_OK)
+    return NAWS_ERR_LAUNCH;
   const int rc = roi_maxmaps(X, N, C, H, W, workspace, workspace + (long long)N * H * W * C, s);
   if (rc != NAWS_OK) return rc;
   hipLaunchKernelGGL((roi_pool_nhwc_xcd_kernel<false, true, 4>), dim3((unsigned)(R * (C / 64))), dim3(256),
-                     (size_t)(64 * pooled_h * pooled_w + 1) * sizeof(float), s, X, C, H, W, rois, R,
-                     boost, pooled_h, pooled_w, spatial_scale, C / 64, Y, RoiPlaneOut{},
+                     lds, s, X, C, H, W, rois, R, boost, pooled_h, pooled_w, spatial_scale, C / 64, Y,
+                     RoiPlaneOut{},
                      (const float*)workspace, (const float*)(workspace + (long long)N * H * W * C));
   return naws_check_launch();
 }
 
-// the pooling launch over block-maxima maps that already exist
+// The operand writers' launch form (waves, rois per workgroup) and its LDS: checked, and the limit
+// raised above 64 KB, by every entry BEFORE it enqueues anything (the maps included), so that an
+// entry that fails leaves nothing behind.
+template <int NWV, int RGV>
+static int roi_planes_lds_ready(int nb) {
+  const size_t lds = roi_xcd_lds(nb, RGV);
+  if (lds > ROI_LDS_MAX) return NAWS_ERR_UNSUPPORTED;          // (RG = 4 of the A/B build only)
+  if (lds > 64 * 1024 &&
+      naws_allow_lds(roi_pool_nhwc_xcd_kernel<true, true, NWV, RGV>) != NAWS_OK)
+    return NAWS_ERR_LAUNCH;
+  return NAWS_OK;
+}
+
+static int roi_planes_ready(int nb) {
+#ifdef NAWS_AB
+  const int nw = naws_knob(NAWS_KNOB_ROI_NW);
+  if (nw == 41) return roi_planes_lds_ready<4, 1>(nb);
+  if (nw == 44) return roi_planes_lds_ready<4, 4>(nb);
+  if (nw == 82) return roi_planes_lds_ready<8, 2>(nb);
+  if (nw == 84) return roi_planes_lds_ready<8, 4>(nb);
+#endif
+  return roi_planes_lds_ready<4, 2>(nb);
+}
+
+// the pooling launch over block-maxima maps that already exist (after roi_planes_ready)
 static int roi_pool_planes_mapped(const float* X, int N, int C, int H, int W, const float* rois,
                                   int R, const float* boost, int pooled_h, int pooled_w,
                                   float spatial_scale, const uint32_t* amax_words, int n_words,
@@ -670,9 +743,8 @@ static int roi_pool_planes_mapped(const float* X, int N, int C, int H, int W, co
 #define NAWS_ROI_LAUNCH(NWV, RGV)                                                                    \
   hipLaunchKernelGGL((roi_pool_nhwc_xcd_kernel<true, true, NWV, RGV>),                               \
                      dim3((unsigned)(naws_cdiv(R, RGV) * (C / 64))), dim3(64 * NWV),                  \
-                     (size_t)(RGV * 64 * pooled_h * pooled_w + RGV) * sizeof(float), s, X, C, H, W,  \
-                     rois, R, boost, pooled_h, pooled_w, spatial_scale, C / 64, (float*)nullptr, po, \
-                     M2, M4)
+                     roi_xcd_lds(pooled_h * pooled_w, RGV), s, X, C, H, W, rois, R, boost, pooled_h,  \
+                     pooled_w, spatial_scale, C / 64, (float*)nullptr, po, M2, M4)
 #ifdef NAWS_AB   // the other (waves, rois per workgroup) forms: A/B build only (tools/bench_roi.py)
   if (nw == 41) NAWS_ROI_LAUNCH(4, 1);
   else if (nw == 44) NAWS_ROI_LAUNCH(4, 4);
@@ -693,7 +765,8 @@ static int roi_pool_planes_check(const float* X, int N, int C, int H, int W, con
   NAWS_REQUIRE_PTR(X); NAWS_REQUIRE_PTR(rois); NAWS_REQUIRE_PTR(amax_words);
   NAWS_REQUIRE_PTR(planes); NAWS_REQUIRE_PTR(scales);
   const long long K = (long long)C * pooled_h * pooled_w;
-  if (C % 64 != 0 || pooled_h * pooled_w > 256 || K % 32 != 0 || (int64_t)R * (C / 64) >= 0x7fffffffLL)
+  if (C % 64 != 0 || pooled_h * pooled_w > ROI_FAST_BINS || K % 32 != 0 ||
+      (int64_t)R * (C / 64) >= 0x7fffffffLL)
     return NAWS_ERR_UNSUPPORTED;
   if ((((uintptr_t)X | (uintptr_t)planes) & 15) != 0) return NAWS_ERR_ARG;
   return NAWS_OK;
@@ -710,6 +783,8 @@ extern "C" int naws_roi_pool_f_f16x2_hier_fwd(const float* X, int N, int C, int 
   if (rc != NAWS_OK) return rc;
   NAWS_REQUIRE_PTR(workspace);
   if (((uintptr_t)workspace & 15) != 0) return NAWS_ERR_ARG;
+  rc = roi_planes_ready(pooled_h * pooled_w);
+  if (rc != NAWS_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* M4 = workspace + (long long)N * H * W * C;
   rc = roi_maxmaps(X, N, C, H, W, workspace, M4, s);
@@ -741,6 +816,7 @@ extern "C" int naws_roi_pool_f_f16x2_mapped_fwd(const float* X, int N, int C, in
   if (rc != NAWS_OK) return rc;
   NAWS_REQUIRE_PTR(M2); NAWS_REQUIRE_PTR(M4);
   if ((((uintptr_t)M2 | (uintptr_t)M4) & 15) != 0) return NAWS_ERR_ARG;
+  if (const int lr = roi_planes_ready(pooled_h * pooled_w); lr != NAWS_OK) return lr;
   return roi_pool_planes_mapped(X, N, C, H, W, rois, R, boost, pooled_h, pooled_w, spatial_scale,
                                 amax_words, n_words, M2, M4, planes, scales, (hipStream_t)stream);
 }
@@ -762,6 +838,7 @@ extern "C" int naws_roi_pool_f_f16x2_mapped_range_fwd(const float* X, int N, int
   if (count == 0) return NAWS_OK;
   NAWS_REQUIRE_PTR(M2); NAWS_REQUIRE_PTR(M4);
   if ((((uintptr_t)M2 | (uintptr_t)M4) & 15) != 0) return NAWS_ERR_ARG;
+  if (const int lr = roi_planes_ready(pooled_h * pooled_w); lr != NAWS_OK) return lr;
   return roi_pool_planes_mapped(X, N, C, H, W, rois, count, boost, pooled_h, pooled_w, spatial_scale,
                                 amax_words, n_words, M2, M4, planes, scales, (hipStream_t)stream, 0,
                                 R_total, r_first);
@@ -780,9 +857,11 @@ extern "C" int naws_roi_pool_f_bf16_slab_mapped_fwd(const float* X, int N, int C
   NAWS_REQUIRE_PTR(X); NAWS_REQUIRE_PTR(rois); NAWS_REQUIRE_PTR(P);
   NAWS_REQUIRE_PTR(M2); NAWS_REQUIRE_PTR(M4);
   const long long K = (long long)C * pooled_h * pooled_w;
-  if (C % 64 != 0 || pooled_h * pooled_w > 256 || K % 64 != 0 || (int64_t)R * (C / 64) >= 0x7fffffffLL)
+  if (C % 64 != 0 || pooled_h * pooled_w > ROI_FAST_BINS || K % 64 != 0 ||
+      (int64_t)R * (C / 64) >= 0x7fffffffLL)
     return NAWS_ERR_UNSUPPORTED;
   if ((((uintptr_t)X | (uintptr_t)P | (uintptr_t)M2 | (uintptr_t)M4) & 15) != 0) return NAWS_ERR_ARG;
+  if (const int lr = roi_planes_ready(pooled_h * pooled_w); lr != NAWS_OK) return lr;
   return roi_pool_planes_mapped(X, N, C, H, W, rois, R, boost, pooled_h, pooled_w, spatial_scale,
                                 nullptr, 1, M2, M4, P, nullptr, (hipStream_t)stream, 1);
 }

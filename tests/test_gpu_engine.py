@@ -13,7 +13,7 @@ def _rel(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
 
 
-def _setup(dev, c=20, dropout=0.5, seed=11, mfma_dtype='fp32'):
+def _setup(dev, c=20, dropout=0.5, seed=11, mfma_dtype='fp32', roi_size=7):
     from detectron.datasets import synthetic
     from naws_hip.engine import WsddnEngine
     roidb = synthetic.make_roidb(2, 24, c, 64, 96, seed=seed)
@@ -21,11 +21,13 @@ def _setup(dev, c=20, dropout=0.5, seed=11, mfma_dtype='fp32'):
     roidb[1]['obn_scores'] = roidb[1]['obn_scores'][:16]
     roidb[1]['gt_classes'] = roidb[1]['gt_classes'][:16]
     mb = synthetic.make_minibatch(roidb, c)
-    blobs = synthetic.init_blobs(c, seed=seed)
+    blobs = synthetic.init_blobs(c, seed=seed, roi_size=roi_size)
     for k in list(blobs):     # non-zero biases so the bias paths are exercised
         if k.endswith('_b'):
             blobs[k] = torch.randn(blobs[k].shape, generator=torch.Generator().manual_seed(1)) * 0.05
-    eng = WsddnEngine(c + 1, dev, dropout=dropout, gpu_num=2, seed=seed, mfma_dtype=mfma_dtype)
+    eng = WsddnEngine(c + 1, dev, dropout=dropout, gpu_num=2, seed=seed, mfma_dtype=mfma_dtype,
+                      roi_size=roi_size)
+    assert eng.k6 == 512 * roi_size ** 2
     eng.set_conv_blobs(blobs)
     eng.set_head_blobs(blobs)
     return eng, mb, blobs
@@ -42,17 +44,21 @@ def _masks(eng, rt, dev):
 
 
 @pytest.mark.parametrize('mode', ['fp32', 'fp32x3', 'fp16x2'])
-@pytest.mark.parametrize('dropout,c', [(0.5, 20), (0.0, 20), (0.5, 80), (0.5, 2), (0.5, 21)])
-def test_engine_matches_oracle(dev, dropout, c, mode):
+@pytest.mark.parametrize('dropout,c,roi_size',
+                         [(0.5, 20, 7), (0.0, 20, 7), (0.5, 80, 7), (0.5, 2, 7), (0.5, 21, 7),
+                          (0.5, 20, 3), (0.5, 20, 5), (0.5, 20, 6)],
+                         ids=['0.5-20', '0.0-20', '0.5-80', '0.5-2', '0.5-21',
+                              '0.5-20-roi3', '0.5-20-roi5', '0.5-20-roi6'])
+def test_engine_matches_oracle(dev, dropout, c, roi_size, mode):
     """Both fp32 plans (fp32 MFMA everywhere / fc6+fc7 as exact 3xbf16 splits on the bf16 MFMA)
-    are held to the same fp32 tolerances."""
+    are held to the same fp32 tolerances; roi_size 3, 5, 6: fc6 at K = 4608, 12800, 18432."""
     from oracle import oracle
-    eng, mb, blobs = _setup(dev, c=c, dropout=dropout, mfma_dtype=mode)
+    eng, mb, blobs = _setup(dev, c=c, dropout=dropout, mfma_dtype=mode, roi_size=roi_size)
     t = {k: torch.from_numpy(v).to(dev) for k, v in mb.items()}
     rt = mb['rois'].shape[0]
     masks = _masks(eng, rt, dev)
     out = eng.forward_backward(t['data'], t['rois'], t['obn_scores'], t['labels_oh'])
-    ref = oracle.full_forward_backward(blobs, mb, masks, c, train=dropout > 0)
+    ref = oracle.full_forward_backward(blobs, mb, masks, c, train=dropout > 0, roi_size=roi_size)
     conv5 = eng.conv_body(t['data']).permute(0, 3, 1, 2)
     assert _rel(conv5, ref['conv5_3']) < 1e-4
     for i in range(2):
@@ -89,18 +95,19 @@ def test_engine_matches_oracle(dev, dropout, c, mode):
         assert (err > tol).mean() <= 2e-3, name
 
 
-@pytest.mark.parametrize('c', [20, 80])
-def test_engine_bf16_mode(dev, c):
+@pytest.mark.parametrize('c,roi_size', [(20, 7), (80, 7), (20, 3), (20, 5), (20, 6)],
+                         ids=['20', '80', '20-roi3', '20-roi5', '20-roi6'])
+def test_engine_bf16_mode(dev, c, roi_size):
     """BASELINE configs[3]: bf16 MFMA conv/fc with fp32 storage and loss.  Operands are rounded
     to 8 significant bits, so conv5_3 / logits / gradients agree with the fp32 oracle to a few
     1e-3 .. 1e-2 (norm-wise), the dropout-free loss to 5e-2, gradients to 15% / cosine 0.99
     (the tight check of the bf16 kernels themselves is tests/test_gpu_bf16.py: 5e-6 against a
     float64 product of the same rounded operands)."""
     from oracle import oracle
-    eng, mb, blobs = _setup(dev, c=c, dropout=0.0, mfma_dtype='bf16')
+    eng, mb, blobs = _setup(dev, c=c, dropout=0.0, mfma_dtype='bf16', roi_size=roi_size)
     t = {k: torch.from_numpy(v).to(dev) for k, v in mb.items()}
     out = eng.forward_backward(t['data'], t['rois'], t['obn_scores'], t['labels_oh'])
-    ref = oracle.full_forward_backward(blobs, mb, None, c, train=False)
+    ref = oracle.full_forward_backward(blobs, mb, None, c, train=False, roi_size=roi_size)
     conv5 = eng.conv_body(t['data']).permute(0, 3, 1, 2).cpu().numpy()
     assert np.linalg.norm(conv5 - ref['conv5_3']) <= 1e-2 * np.linalg.norm(ref['conv5_3'])
     for i in range(2):
@@ -154,16 +161,18 @@ def test_engine_sgd_steps(dev, mode):
         assert np.abs(m_got - m_ref).max() <= 2e-3 * np.abs(m_ref).max() + 1e-9, name
 
 
-@pytest.mark.parametrize('mode', ['fp32', 'fp32x3', 'fp16x2'])
-def test_engine_infer(dev, mode):
+@pytest.mark.parametrize('mode,roi_size', [(m, 7) for m in ('fp32', 'fp32x3', 'fp16x2')]
+                         + [(m, 6) for m in ('fp32', 'fp32x3', 'fp16x2')],
+                         ids=['fp32', 'fp32x3', 'fp16x2', 'fp32-roi6', 'fp32x3-roi6', 'fp16x2-roi6'])
+def test_engine_infer(dev, mode, roi_size):
     from oracle import oracle
-    eng, mb, blobs = _setup(dev, dropout=0.5, mfma_dtype=mode)
+    eng, mb, blobs = _setup(dev, dropout=0.5, mfma_dtype=mode, roi_size=roi_size)
     t = {k: torch.from_numpy(v).to(dev) for k, v in mb.items()}
     one = {k: v[:1] if k in ('data', 'labels_oh') else v for k, v in mb.items()}
     sel = mb['rois'][:, 0] == 0
     cls_prob = eng.infer(t['data'][:1], t['rois'][sel], t['obn_scores'][sel])
     one['rois'], one['obn_scores'] = mb['rois'][sel], mb['obn_scores'][sel]
-    ref = oracle.full_forward_backward(blobs, one, None, 20, train=False)
+    ref = oracle.full_forward_backward(blobs, one, None, 20, train=False, roi_size=roi_size)
     rp = ref['tails'][0]['rois_pred']
     np.testing.assert_allclose(cls_prob.cpu().numpy(), np.concatenate([rp[:, :1], rp], 1),
                                rtol=1e-4, atol=1e-8)
@@ -338,14 +347,30 @@ def test_weight_planes_written_by_the_update_equal_a_fresh_split(dev, mode):
     assert torch.equal(runs[True][0], runs[False][0]) and torch.equal(runs[True][1], runs[False][1])
 
 
+# roi_size -> the column where fc6's wgrad over one 8192-row chunk is cut (engine._wgrad_column_cut):
+# both arms of _fc6_wgrad_cut and a 512-column remainder after 16, 48 and 96 column tiles
+WGRAD_CUT = {3: 4096, 5: 12288, 6: 0, 7: 24576}
+
+
 def test_train_step_updates_fc6_in_the_wgrad_epilogue_bit_identically(dev):
     """train_step(): with no gradient exchange fc6_w's update runs inside its weight-gradient
     GEMM (no gradient blob, engine.train_step).  Parameters, momentum and all three operand plane
     sets after four iterations (an lr change in between) equal forward_backward() + sgd_step()
     bit for bit; the fused route really ran (its gradient slot stays untouched)."""
+    _train_step_fp16x2_epilogue(dev, 7)
+
+
+@pytest.mark.parametrize('roi_size', [3, 5, 6])
+def test_train_step_updates_fc6_in_the_wgrad_epilogue_bit_identically_at_roi_size(dev, roi_size):
+    """The same at fc6 K = 4608, 12800 (cut, 512 columns left) and 18432 (no cut)."""
+    _train_step_fp16x2_epilogue(dev, roi_size)
+
+
+def _train_step_fp16x2_epilogue(dev, roi_size):
     res = []
     for fused in (False, True):
-        eng, mb, _blobs = _setup(dev, mfma_dtype='fp16x2')
+        eng, mb, _blobs = _setup(dev, mfma_dtype='fp16x2', roi_size=roi_size)
+        assert eng._wgrad_column_cut(8192) == WGRAD_CUT[roi_size]
         eng.fuse_wgrad_update = fused
         t = {k: torch.from_numpy(v).to(dev) for k, v in mb.items()}
         eng.set_lr(1e-3)
@@ -377,9 +402,19 @@ def test_train_step_bf16_plan_updates_fc6_in_the_wgrad_epilogue_bit_identically(
     """The bf16 plan's form of the same route (ops.gemm_bf16_slab_nt_sgd): parameters, momentum and
     the rounded operand planes after four iterations equal forward_backward() + sgd_step() bit for
     bit, and the fused route really ran."""
+    _train_step_bf16_epilogue(dev, 7)
+
+
+@pytest.mark.parametrize('roi_size', [3, 5, 6])
+def test_train_step_bf16_plan_updates_fc6_in_the_wgrad_epilogue_bit_identically_at_roi_size(
+        dev, roi_size):
+    _train_step_bf16_epilogue(dev, roi_size)
+
+
+def _train_step_bf16_epilogue(dev, roi_size):
     res = []
     for fused in (False, True):
-        eng, mb, _blobs = _setup(dev, mfma_dtype='bf16')
+        eng, mb, _blobs = _setup(dev, mfma_dtype='bf16', roi_size=roi_size)
         eng.fuse_wgrad_update = fused
         t = {k: torch.from_numpy(v).to(dev) for k, v in mb.items()}
         eng.set_lr(1e-3)
@@ -539,10 +574,18 @@ def test_per_image_pooling_on_the_conv_streams_is_bit_identical(dev):
     chain (naws_roi_pool_f_f16x2_mapped_range_fwd on the image's stream): fc6's operand planes and
     scales, the losses and every gradient equal the one-launch-after-the-join route bit for bit;
     ragged proposal counts, one image without proposals of its own in the middle of the batch."""
+    _per_image_pooling(dev, 7)
+
+
+def test_per_image_pooling_on_the_conv_streams_is_bit_identical_at_roi_size_3(dev):
+    _per_image_pooling(dev, 3)
+
+
+def _per_image_pooling(dev, roi_size):
     from detectron.datasets import synthetic
     from naws_hip.engine import WsddnEngine
     c = 20
-    blobs = synthetic.init_blobs(c, seed=3)
+    blobs = synthetic.init_blobs(c, seed=3, roi_size=roi_size)
     roidb = synthetic.make_roidb(3, 40, c, 64, 96, seed=4)
     for e, r in zip(roidb, (37, 5, 40)):
         for k in ('boxes', 'obn_scores', 'gt_classes'):
@@ -552,7 +595,8 @@ def test_per_image_pooling_on_the_conv_streams_is_bit_identical(dev):
     seg = [0, 37, 42, 82]
     res = []
     for on in (True, False):
-        eng = WsddnEngine(c + 1, dev, dropout=0.5, gpu_num=3, seed=3, mfma_dtype='fp16x2')
+        eng = WsddnEngine(c + 1, dev, dropout=0.5, gpu_num=3, seed=3, mfma_dtype='fp16x2',
+                          roi_size=roi_size)
         eng.ROI_POOL_ON_CHAINS = on
         eng.set_conv_blobs(blobs)
         eng.set_head_blobs(blobs)
